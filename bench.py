@@ -16,8 +16,13 @@ the GPU.  --gpus must equal WORLD_SIZE under a launcher, and RCCL ranks may not 
 both exit non-zero with a message instead of printing a mislabelled line.
 
 Prints ONE JSON line on rank 0 (contract in the task statement), with `roofline` (dominant kernel:
-the persistent trace kernel, timed with HIP events on the launch stream) and `cpu_baseline` (the f64
-C oracle on the host cores, bounded sample).
+the persistent trace kernel, timed with HIP events on the launch stream, read from the timed steps' own
+counters).  A plain run sets up, warms up, times the steps and prints that line.  `--full` adds, after the
+timed region, everything else the benchmark measures or checks: `cpu_baseline` (the f64 C oracle on the
+host cores, bounded sample), `configs` (one frame of BASELINE.json's other configs with their CPU legs;
+at N > 1 config 5 sharded over the job's GPUs) and at N > 1 `multi_rank_check` (a small frame through the
+job's exchange against one device's frame).  `--dump-outputs DIR` writes the last timed step's frame (the
+[H][W][3] f64 sums in host memory, what a caller of the timed path receives) as DIR/accum.npy.
 """
 import argparse
 import json
@@ -63,9 +68,14 @@ def parse():
     ap.add_argument("--cpu-config-seconds", type=float, default=5.0,
                     help="target wall time of each other config's CPU leg (configs 3-5: full frame, reduced spp)")
     ap.add_argument("--cpu-threads", type=int, default=0, help="0 = every core this process may use (cgroup-aware)")
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the CPU baseline, BASELINE.json's other configs and, at N > 1, "
+                         "the multi-rank frame check (off by default: a plain run measures the headline only)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU-baseline legs")
     ap.add_argument("--no-configs", action="store_true",
-                    help="skip the one-frame measurements of BASELINE.json's other configs (N=1 only)")
+                    help="with --full: skip the one-frame measurements of BASELINE.json's other configs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last step's outputs (rank 0's frame sums) as DIR/<name>.npy")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="collective backend for N>1 (gloo only to rehearse several ranks on one GPU)")
     ap.add_argument("--rank-env-only", action="store_true",
@@ -370,6 +380,23 @@ def multi_rank_check(args, dev, comm, rank, world, torch, rt):
     return res
 
 
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000 - 4096  # --dump-outputs: array bytes in all (64 MB less room for the .npy header)
+
+
+def dump_outputs(path, frame):
+    """--dump-outputs: the last timed step's frame ([H][W][3] f64 per-pixel sums, as they reached host
+    memory) as <path>/accum.npy.  A frame above DUMP_LIMIT_BYTES is written as a fixed sample of its pixels
+    (seeded, so two runs with the same arguments keep the same pixels, in ascending pixel order): [n][3]."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    a = np.ascontiguousarray(frame, dtype=np.float64)
+    if a.nbytes > DUMP_LIMIT_BYTES:
+        px = a.reshape(-1, a.shape[-1])
+        n = DUMP_LIMIT_BYTES // (px.shape[1] * px.itemsize)
+        a = px[np.sort(np.random.default_rng(0x5EED).choice(px.shape[0], size=n, replace=False))]
+    np.save(os.path.join(path, "accum.npy"), a)
+
+
 def valu_block(segments, k_ms, W, H, args):
     """The measured ceiling of the trace kernel (VALU issue x lane utilisation), from the committed PMC
     passes (profiles/valu.json, written by tools/pmc_valu.py from profiles/<round>/pmc_valu_*.csv of one
@@ -499,6 +526,9 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
+    if args.dump_outputs and rank == 0:  # (the synchronize above completed the last step's copy to the host)
+        dump_outputs(args.dump_outputs, host_accum.numpy())
+
     total_samples = W * H * args.spp * args.steps
     value = total_samples / elapsed / 1e6
     # per trace-kernel launch (a frame whose partial sums exceed the scratch bound runs in several sample
@@ -563,15 +593,16 @@ def main():
         "cpu_baseline": None,
     }
     mrc = None
-    if world > 1:  # (after the timed region: the exchange of this job checked against one device's frame)
+    # --full legs, all after the timed region.  N > 1: the job's exchange checked against one device's frame
+    if world > 1 and args.full:
         mrc = multi_rank_check(args, dev, comm, rank, world, torch, rt)
         if rank == 0:
             line["multi_rank_check"] = mrc
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu:
         line["cpu_baseline"] = cpu_baseline(scene, cam, args)
-    if world == 1 and not args.no_configs:  # (after the timed region; the headline scene is replaced)
+    if world == 1 and args.full and not args.no_configs:  # (the headline scene is replaced)
         line["configs"] = configs_block(args, dev, torch, rt)
-    if comm is not None and not args.no_configs:  # config 5 at its stated scale: sharded over the job's GPUs
+    if comm is not None and args.full and not args.no_configs:  # config 5 at its stated scale: sharded over the GPUs
         try:
             line["configs"] = sharded_config5(args, dev, comm, rank, world, torch, dist, rt)
         except Exception as e:  # (an extra leg: it must not cost the headline line)

@@ -119,6 +119,36 @@ def test_resolve_partition():
     assert b.resolve_partition("auto", {"SHIRLEY_PARTITION": "samples"}) == "samples"
 
 
+def test_full_is_off_by_default(monkeypatch):
+    """A plain run measures the headline only; the other legs need --full."""
+    b = _bench()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1"])
+    a = b.parse()
+    assert a.full is False and a.dump_outputs is None and a.steps == 2 and a.warmup == 1
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = b.parse()
+    assert a.full is True and a.dump_outputs == "d"
+
+
+def test_dump_outputs_writes_the_frame_or_a_fixed_sample(tmp_path, monkeypatch):
+    """--dump-outputs: the frame as float64 accum.npy, unchanged; above the size limit a seeded sample of
+    its pixels, the same pixels on every run, within the limit."""
+    import numpy as np
+    b = _bench()
+    assert b.DUMP_LIMIT_BYTES <= 64 * 1000 * 1000
+    frame = np.random.default_rng(3).random((10, 14, 3)) * 500.0
+    b.dump_outputs(str(tmp_path / "a"), frame)
+    got = np.load(tmp_path / "a" / "accum.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, frame)
+    monkeypatch.setattr(b, "DUMP_LIMIT_BYTES", 50 * 24)
+    b.dump_outputs(str(tmp_path / "b"), frame)
+    b.dump_outputs(str(tmp_path / "c"), frame)
+    s1, s2 = np.load(tmp_path / "b" / "accum.npy"), np.load(tmp_path / "c" / "accum.npy")
+    assert s1.shape == (50, 3) and s1.nbytes <= 50 * 24 and np.array_equal(s1, s2)
+    px = {tuple(p) for p in frame.reshape(-1, 3)}
+    assert all(tuple(p) in px for p in s1) and len({tuple(p) for p in s1}) == 50
+
+
 def test_cpu_leg_sizes_the_frame_to_the_time_budget():
     """bench.py's per-config CPU legs (configs 3-5, BASELINE.md:24,33-35): the oracle over the full frame
     at an spp sized to the time budget, never above the config's own spp."""

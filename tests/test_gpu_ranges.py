@@ -1,6 +1,6 @@
 """ABI 6 on the GPU: the sample range of rt_render_params ("tile rect / sample range"),
 the sample passes that bound the partial-sum scratch, the sample partition of the multi-GPU calls and the
-scene-digest check (reference: the per-pixel sample loop, /root/reference/src/raytracer/render.rs:58-69).
+scene-digest check (reference: the per-pixel sample loop, src/raytracer/render.rs:58-69).
 
 * A range [b, e) renders exactly the samples b..e-1 of every pixel: with sample_chunk >= e - b its
   per-pixel sums equal the oracle's in-order sums over the same range (the oracle's render_scanline

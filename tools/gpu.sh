@@ -8,7 +8,8 @@
 #   testsd[:pytest args]     the same, verbose, with per-test timeouts and a parity log
 #   testsv:<variant>[:args]  the same against exp/<variant>'s libraries (SHIRLEY_LIB_DIR)
 #   smoke                    __graft_entry__.smoke()
-#   bench[:bench.py args]    one bench line (default: the driver's defaults)
+#   bench[:bench.py args]    one bench line (default: the driver's defaults, the headline only; "bench:--full"
+#                            adds the CPU baseline and the other configs)
 #   ab:<spec>;<spec>;...     interleaved A/B, one bench line per spec "variant|ENV=V ...|bench flags"
 #                            (variant "main" = the in-tree build, else exp/<variant>, see tools/variant.sh);
 #                            AB_REPS (default 2) rounds over the specs, AB_STEPS (default 3) steps each

@@ -11,7 +11,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 run() {  # run <N> <label> <bench args...>
   local n=$1 label=$2
   shift 2
-  timeout -k 10 300 python -u bench.py --gpus "$n" --dist-backend gloo --steps 2 --warmup 1 --no-cpu --no-configs "$@" \
+  timeout -k 10 300 python -u bench.py --gpus "$n" --dist-backend gloo --steps 2 --warmup 1 --full --no-cpu --no-configs "$@" \
     > "$out/rehearsal_${n}_${label}.log" 2>&1 || { echo "rehearsal $n $label failed"; tail -20 "$out/rehearsal_${n}_${label}.log"; return 1; }
   tail -1 "$out/rehearsal_${n}_${label}.log" >> "$out/rehearsal_${n}.jsonl"
   tail -1 "$out/rehearsal_${n}_${label}.log" | python3 -c 'import sys, json
