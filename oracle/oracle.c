@@ -669,7 +669,7 @@ static int texture_uses_uv(const rt_scene_desc* d, int32_t ti) {
  * centre, so such an instance is flattened into a world-space sphere before anything else reads it —
  * centre (cs cx + sn cz + off.x, cy + off.y, -sn cx + cs cz + off.z), the same formula that maps an
  * instance's hit point back to the world (ext_object_hit) — and takes the reference sphere path.  The
- * host (rt_api.cpp flat_object) flattens by the same rule.  t, point and normal agree with per-ray
+ * host (scene_compile.cpp flat_object) flattens by the same rule.  t, point and normal agree with per-ray
  * instancing in real arithmetic (the records differ at the last bit); u, v do not under a
  * rotation, so a rotated sphere is flattened only when its material never reads them, and keeps its
  * angle (transform = 0) for the hit query's u, v (or_scene_hit_at). */

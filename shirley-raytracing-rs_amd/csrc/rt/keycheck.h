@@ -2,7 +2,7 @@
 // the decisions can be driven on the CPU (tests/test_keycheck.py through tools/keycheck_sim.cpp).
 //
 // Every rank must render the same scene with the same call key (scene digest + resolved partition, sample
-// range and render arguments, rt_api.cpp call_key).  Every call, on every rank, all-gathers the 16-byte
+// range and render arguments, rt_multi.cpp call_key).  Every call, on every rank, all-gathers the 16-byte
 // (digest, key) words — so all ranks issue one and the same collective sequence whatever their arguments —
 // and the gathered words are checked on the host:
 //   * now (before the frame's collectives are issued) when this rank's key differs from the one the ranks

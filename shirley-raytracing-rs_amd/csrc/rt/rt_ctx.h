@@ -1,0 +1,141 @@
+// rt_ctx.h — the context behind the C ABI's opaque rt_ctx / rt_comm, and the helpers that rt_api.cpp
+// (scene, render, queries) and rt_multi.cpp (multi-GPU) share.  Internal to the library.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cstdarg>
+#include <cstdio>
+#include <string>
+#include <utility>
+#include <vector>
+
+#include "../../../include/shirley_rt.h"
+#include "keycheck.h"
+#include "rccl_loader.h"
+#include "rt_launch.h"
+#include "rt_layout.h"
+#include "scene_compile.h"
+
+struct DevBuf {
+  void* p = nullptr;
+  size_t bytes = 0;
+};
+
+// A rank of an RCCL communicator (multi-GPU frame sharding).
+struct rt_comm {
+  ncclComm_t comm = nullptr;
+  int world = 1, rank = 0, device = 0;
+  // rt_render_sharded's cross-rank check (keycheck.h): the key the ranks last agreed on, and the gathered
+  // (digest, key) words of the last two calls in pinned host memory ([2 slots][world + 1][2]: the gathered
+  // words, then this rank's own), each slot's copy marked by an event
+  rt::KeyState ks;
+  uint64_t* key_words = nullptr;
+  hipEvent_t key_ev[2] = {nullptr, nullptr};
+  int key_slot = 0;       // slot of the next call
+  int key_pending = 0;    // slot of the pending (deferred) check
+};
+
+struct rt_ctx {
+  int device = 0;
+  hipStream_t stream = nullptr;
+  std::string err;
+  int cu_count = 0;
+  // scene
+  bool have_scene = false;
+  rt::DScene scene{};
+  DevBuf nodes, nodes4, prims, mats, texs, perlin, texels, exts;
+  rt_scene_stats stats{};
+  int blocks_per_cu = 0;
+  rt::ScenePlacement place;        // the uploaded scene's plan (place.mk_threads: the megakernel block size)
+  int split_nt = 0;                // RT_ENGINE_SPLIT: traversal waves per block (0: scene not eligible)
+  int split_refill = 8;            // idle traversal lanes before a traversal wave claims rays
+  // wavefront engine: the scene with its LDS node count sized for the extend block
+  rt::DScene wf_scene{};
+  int wf_blocks_per_cu = 0;
+  bool wf_wide = false;      // wavefront extend runs the 4-wide scene-in-LDS kernel (wf_extend4)
+  int wf4_blocks_per_cu = 0;
+  bool has_perlin = false;
+  int n_perlin = 0;
+  // per-render scratch
+  DevBuf partial, accum, counters, unit_counter, kcam;
+  DevBuf shutter0;  // {0, 0}: the shutter of rt_scene_hit / rt_probe_segment queries (DScene.shutter)
+  DevBuf wf_pool, wf_iters;          // path slots (SoA) + texture queue; per-iteration counters ring
+  uint32_t* wf_host = nullptr;       // pinned readback of the retired-slot count, one word per batch
+  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+  hipEvent_t wf_ev[2] = {nullptr, nullptr};
+  std::vector<hipEvent_t> lap_ev;    // RT_ENGINE_TIMING: one event after every launch
+  bool have_timing = false;
+  int last_engine = 0, last_iters = 0, last_timing = 0, last_chunk = 0, last_n_chunks = 0, last_passes = 0;
+  uint64_t last_slots = 0, last_scratch = 0;
+  std::vector<hipEvent_t> pass_ev;   // before / after the trace launch of each sample pass
+  std::vector<rt::KBlock> host_blocks;    // host sources of the device KBlocks (KParams.kconst)
+  uint64_t digest = 0;               // rt_scene_digest of the uploaded scene
+  // device primitive number -> object index (primitives are numbered in the reference tree's leaf order)
+  std::vector<int32_t> prim_object;
+  // flattened rotated spheres (flat_object): object index -> RotateY's cos, sin, for rt_scene_hit's u, v
+  std::vector<std::pair<int32_t, std::pair<double, double>>> uv_fixups;
+  uint64_t host_samples = 0;  // samples of a frame served without a trace kernel (max_depth == 0)
+  double lap_ms[3] = {0, 0, 0};
+  // multi-GPU: this rank's packed tiles, the root's gathered buffer, and (root of rt_render_multi)
+  // the communicators of the device set last used, kept for the next call
+  DevBuf packed, gathered, parts, band, digests;
+  std::vector<int> group_devices;
+  std::vector<rt_comm> group_comms;
+};
+
+namespace rt {
+
+inline int fail(rt_ctx* c, int code, const char* fmt, ...) {
+  char buf[512];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(buf, sizeof buf, fmt, ap);
+  va_end(ap);
+  if (c) c->err = buf;
+  return code;
+}
+
+#define HIP_TRY(ctx, expr)                                                                      \
+  do {                                                                                          \
+    hipError_t e_ = (expr);                                                                     \
+    if (e_ != hipSuccess)                                                                       \
+      return fail(ctx, e_ == hipErrorOutOfMemory ? RT_E_OOM : RT_E_HIP, "%s: %s (%s:%d)", #expr, \
+                  hipGetErrorString(e_), __FILE__, __LINE__);                                   \
+  } while (0)
+
+// rt_api.cpp
+int ensure(rt_ctx* c, DevBuf& b, size_t bytes);
+void release(DevBuf& b);
+int upload(rt_ctx* c, DevBuf& b, const void* src, size_t bytes);
+
+inline int resolve_stream(rt_ctx* c, void* stream, hipStream_t* out) {
+  *out = stream ? reinterpret_cast<hipStream_t>(stream) : c->stream;
+  return RT_OK;
+}
+
+struct Layout {
+  int tiles_x, tiles_y, n_tiles, n_tiles_rank;
+};
+
+inline Layout layout(const rt_camera* cam, int ty0, int ty1, int rank, int world) {
+  Layout L;
+  L.tiles_x = (cam->image_width + kTile - 1) / kTile;
+  L.tiles_y = ty1 - ty0;
+  L.n_tiles = L.tiles_x * L.tiles_y;
+  L.n_tiles_rank = (L.n_tiles > rank) ? (L.n_tiles - rank + world - 1) / world : 0;
+  return L;
+}
+
+// The sample range [begin, end) of a call (rt_render_params.sample_begin / sample_count, ABI 6).
+struct SampleRange {
+  int begin = 0, end = 0;
+};
+
+// rt_api.cpp
+int check_render_args(rt_ctx* c, const rt_camera* cam, const rt_render_params* p);
+int resolve_range(rt_ctx* c, const rt_render_params* p, SampleRange* r);
+int render_window(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, const SampleRange& R, int ty0, int ty1,
+                  int row0, int row1, int packed, double* out_dev, hipStream_t s);
+
+}  // namespace rt

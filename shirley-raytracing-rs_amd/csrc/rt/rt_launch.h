@@ -1,0 +1,47 @@
+// rt_launch.h — the launch wrappers of the HIP files, as the host side of the C ABI calls them.
+//
+// Included by rt_api.cpp / rt_multi.cpp and by the files that define the wrappers (trace.hip,
+// trace_split.hip, wavefront.hip), so a changed signature fails to compile where it is changed.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include "rt_layout.h"
+
+namespace rt {
+// trace.hip
+hipError_t trace_occupancy(const DScene& S, int threads, int* blocks_per_cu);
+hipError_t launch_trace(const KParams& p, int blocks, int threads, hipStream_t stream);
+#ifdef RT_PHASE_TIMING
+void phase_counters_dump();
+#endif
+#ifdef RT_TIMELINE
+void timeline_dump();
+#endif
+hipError_t launch_reduce(const double* partial, int n_chunks, int n_tiles_rank, int tiles_x, int ty0, int tile_rank,
+                         int tile_world, int width, int row0, int row1, int packed, int accumulate, double* out,
+                         hipStream_t stream);
+hipError_t launch_tonemap(const double* accum, int width, int height, double inv, uint8_t* rgb8, hipStream_t stream);
+hipError_t launch_unpack(const double* gathered, int world, int max_tiles, int n_tiles_total, int tiles_x, int width,
+                         int height, double* out, hipStream_t stream);
+hipError_t launch_sum_parts(const double* parts, int n_parts, long long n, double* out, hipStream_t stream);
+hipError_t launch_hit(const DScene& S, const double* rays, int n, double t_min, double t_max, void* out,
+                      hipStream_t stream);
+hipError_t launch_hit4(const DScene& S, bool wide, const double* rays, int n, double t_min, double t_max, void* out,
+                       hipStream_t stream);
+hipError_t launch_probe(const DScene& S, bool wide, const double* rays, int n, uint64_t seed, uint32_t sample,
+                        uint32_t draw, void* out, hipStream_t stream);
+// trace_split.hip
+bool split_supported_nt(int nt);
+hipError_t split_prepare(const DScene& S, int nt, int* blocks_per_cu);
+hipError_t launch_split(const KParams& p, int nt, int blocks, hipStream_t stream);
+// wavefront.hip
+int wf_grid_threads();
+hipError_t wf_prepare(const DScene& S, int* extend_blocks_per_cu);
+hipError_t wf_prepare4(const DScene& S, int* extend_blocks_per_cu);
+hipError_t wf_launch_extend4(const WfParams& P, int extend_blocks, hipStream_t s);
+hipError_t wf_start(const WfParams& P, int grid_blocks, hipStream_t s);
+hipError_t wf_launch_extend(const WfParams& P, int extend_blocks, hipStream_t s);
+hipError_t wf_launch_shade(const WfParams& P, int grid_blocks, hipStream_t s);
+hipError_t wf_launch_texture(const WfParams& P, int grid_blocks, hipStream_t s);
+}  // namespace rt

@@ -1,10 +1,11 @@
 // rt_layout.h — HBM layout of a flattened scene and the trace-kernel parameter block.
 //
-// Shared by the host side of the C ABI (rt_api.cpp, bvh_build.cpp) and the HIP kernels
+// Shared by the host side of the C ABI (rt_api.cpp, scene_compile.cpp, bvh_build.cpp) and the HIP kernels
 // (trace.hip).  Plain structs only; sizes are checked with static_assert so host and device
 // agree byte for byte.
 #pragma once
 
+#include <stddef.h>
 #include <stdint.h>
 
 #include "plan.h"  // (unit window sizes)
@@ -21,6 +22,7 @@ constexpr int kTraceThreadsWide = 1024; // megakernel block holding the whole BV
 #endif
 constexpr int kTraceThreadsWide3 = RT_EXT_WIDE_THREADS;  // book-2 (EXT) scenes' wide block: 768 = 3 waves per SIMD (168 VGPRs)
 constexpr int kHitThreads = 256;    // rt_scene_hit kernel
+constexpr int kExtendThreads = 256; // wf_extend block (wavefront.hip): 4 waves per block, several blocks per CU
 constexpr int kWave = 64;
 constexpr int kLdsBytes = 160 * 1024;  // LDS per CU (gfx950)
 
@@ -99,7 +101,7 @@ struct alignas(16) DExt {
   double off[3];            // Translate offset
   double neg_inv_density;   // ConstantMedium: -1 / density
   int32_t object;           // the object's index in the scene description (its side-stream key; primitives
-                            //   are numbered by the reference's leaf order, rt_api.cpp)
+                            //   are numbered by the reference's leaf order, scene_compile.cpp)
   int32_t prim;             // its primitive number (the deferred object tests, rt_device.h ext_deferred)
 };
 static_assert(sizeof(DExt) == 144, "DExt layout");
@@ -142,6 +144,21 @@ struct DPerlin {
   double ranfloat[256][3];
   int32_t perm_x[256], perm_y[256], perm_z[256];
 };
+
+// LDS bytes of one block, by the one formula the placement plan (scene_compile.cpp) and the launch
+// wrappers (trace.hip, wavefront.hip) share.
+// megakernel block LDS: [n_lds_nodes4 x node4_bytes][n_lds_prims x DPrim][n_lds_perlin x DPerlin]
+// [n_lds_mats x DMat][n_lds_texs x DTex][stack_depth4 x threads packed entries]
+inline size_t trace_lds_bytes(int n_lds_nodes4, int node4_size, int n_lds_prims, int n_lds_perlin, int stack_depth4,
+                              int threads, int n_lds_mats, int n_lds_texs) {
+  return (size_t)n_lds_nodes4 * node4_size + (size_t)n_lds_prims * sizeof(DPrim) +
+         (size_t)n_lds_perlin * sizeof(DPerlin) + (size_t)n_lds_mats * sizeof(DMat) + (size_t)n_lds_texs * sizeof(DTex) +
+         (size_t)stack_depth4 * threads * kStack4EntryBytes;
+}
+// wf_extend block LDS: [n_lds_nodes x DNode][stack_depth x kExtendThreads x (node, t) entries]
+inline size_t wf_extend_lds(int n_lds_nodes, int stack_depth) {
+  return (size_t)n_lds_nodes * sizeof(DNode) + (size_t)stack_depth * kExtendThreads * 8;
+}
 
 struct DScene {
   const DNode* nodes;      // node 0 = top node (child[0] = root, child[1] = empty)

@@ -18,6 +18,7 @@
 //     wave (marble_coop, random_in_unit_sphere_coop);
 //   * per-unit partial sums go to HBM once; a reduce kernel sums chunks in order (deterministic).
 #include "rt_device.h"
+#include "rt_launch.h"
 
 #include <algorithm>
 #include <vector>
@@ -723,16 +724,9 @@ __global__ __launch_bounds__(kHitThreads) void probe_kernel(DScene S, const doub
 }
 
 // ------------------------------------------------------------------------------------------
-// launch wrappers (called from rt_api.cpp)
+// launch wrappers (declared in rt_launch.h, called from rt_api.cpp)
 // ------------------------------------------------------------------------------------------
-// megakernel block LDS: [n_lds_nodes4 x node4_bytes][n_lds_prims x DPrim][n_lds_perlin x DPerlin]
-// [stack_depth4 x threads packed entries]
-size_t trace_lds_bytes(int n_lds_nodes4, int node4_size, int n_lds_prims, int n_lds_perlin, int stack_depth4,
-                       int threads, int n_lds_mats, int n_lds_texs) {
-  return (size_t)n_lds_nodes4 * node4_size + (size_t)n_lds_prims * sizeof(DPrim) +
-         (size_t)n_lds_perlin * sizeof(DPerlin) + (size_t)n_lds_mats * sizeof(DMat) + (size_t)n_lds_texs * sizeof(DTex) +
-         (size_t)stack_depth4 * threads * kStack4EntryBytes;
-}
+// (megakernel block LDS: trace_lds_bytes, rt_layout.h)
 size_t hit_lds_bytes(int n_lds_nodes, int stack_depth) { return lds_bytes(n_lds_nodes, stack_depth, kHitThreads); }
 
 static int node_mode(const DScene& S) {
@@ -784,7 +778,7 @@ hipError_t trace_occupancy(const DScene& S, int threads, int* blocks_per_cu) {
     if (S.n_lds_prims > 0) return occupancy_impl1<kTraceThreadsWide, kSceneLds, false>(S, blocks_per_cu);
     return occupancy_impl1<kTraceThreadsWide, kNodesLds, false>(S, blocks_per_cu);
   }
-  if (threads == kTraceThreadsWide3) {  // book-2 scenes only (rt_api.cpp)
+  if (threads == kTraceThreadsWide3) {  // book-2 scenes only (scene_compile.cpp)
     if (node_mode4(S) != kNodesLds || !S.exts) return hipErrorInvalidValue;
     if (S.n_lds_prims > 0) return occupancy_impl1<kTraceThreadsWide3, kSceneLds, true>(S, blocks_per_cu);
     return occupancy_impl1<kTraceThreadsWide3, kNodesLds, true>(S, blocks_per_cu);

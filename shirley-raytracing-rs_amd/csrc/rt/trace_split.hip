@@ -27,6 +27,7 @@
 // is drained and none of its lanes holds a path; it then decrements `live`; traversal waves leave
 // when `live` is 0 (no request can be pending then) — every wave reaches its exit.
 #include "rt_device.h"
+#include "rt_launch.h"
 
 namespace rt {
 
@@ -355,7 +356,7 @@ __global__ __launch_bounds__(kTraceThreadsWide, 1) void split_kernel(KParams P) 
 }
 
 // ------------------------------------------------------------------------------------------
-// launch wrappers (rt_api.cpp): the split kernel serves reference scenes (no book-2 primitives)
+// launch wrappers (rt_launch.h; called from rt_api.cpp): the split kernel serves reference scenes (no book-2 primitives)
 // whose whole scene (4-wide tree, primitives, Perlin tables) fits in LDS next to the traversal
 // stacks and the ray slots.
 // ------------------------------------------------------------------------------------------

@@ -18,13 +18,13 @@
 // Arithmetic is binary64 and identical to the megakernel (rt_device.h), so both engines produce the
 // same pixels; counter-based RNG keyed by (pixel, sample) makes them independent of scheduling.
 #include "rt_device.h"
+#include "rt_launch.h"
 
 namespace rt {
 
 enum : uint8_t { kSlotIdle = 0, kSlotAlive = 1, kSlotEnded = 2, kSlotRetired = 3 };
 enum : int32_t { kDeferLambertian = 0, kDeferFairy = 1, kDeferDiffuse = 2 };
 constexpr uint32_t kNoUnit = 0xffffffffu;
-constexpr int kExtendThreads = 256;  // 4 waves per block, several blocks per CU
 constexpr int kGridThreads = 256;
 
 __device__ __forceinline__ unsigned long long wf_lanemask_lt() {
@@ -566,21 +566,17 @@ __global__ __launch_bounds__(kGridThreads) void wf_texture(WfParams P) {
 }
 
 // ------------------------------------------------------------------------------------------
-// host-side launch helpers (called from rt_api.cpp)
+// host-side launch helpers (declared in rt_launch.h, called from rt_api.cpp)
 // ------------------------------------------------------------------------------------------
-size_t wf_extend_lds(int n_lds_nodes, int stack_depth) {
-  return (size_t)n_lds_nodes * sizeof(DNode) + (size_t)stack_depth * kExtendThreads * 8;
-}
-
-int wf_extend_threads() { return kExtendThreads; }
-
+// (wf_extend block LDS: wf_extend_lds, rt_layout.h)
 static int wf_mode(const DScene& S) {
   return S.n_lds_nodes >= S.n_nodes ? kNodesLds : (S.n_lds_nodes == 0 ? kNodesGlobal : kNodesMixed);
 }
 
+// the megakernel's LDS layout without the material tables, for a kTraceThreadsWide block
 size_t wf_extend4_lds(const DScene& S) {
-  return (size_t)S.n_lds_nodes4 * node4_bytes(S.exts != nullptr) + (size_t)S.n_lds_prims * sizeof(DPrim) +
-         (size_t)S.n_lds_perlin * sizeof(DPerlin) + (size_t)S.stack_depth4 * kTraceThreadsWide * kStack4EntryBytes;
+  return trace_lds_bytes(S.n_lds_nodes4, node4_bytes(S.exts != nullptr), S.n_lds_prims, S.n_lds_perlin, S.stack_depth4,
+                         kTraceThreadsWide, 0, 0);
 }
 
 // Kernel instances come in pairs: EXT = the scene has book-2 primitives (their out-of-line code

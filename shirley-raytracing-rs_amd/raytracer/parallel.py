@@ -63,7 +63,7 @@ def gather_tiles(packed, world: int):
 
 # ---- sample partition (RT_PARTITION_SAMPLES): the same exchange as rt_render_sharded's -------------
 def sample_share(begin: int, end: int, rank: int, world: int):
-    """Rank `rank`'s part [b, e) of the frame's sample range [begin, end) (rt_api.cpp shard_render)."""
+    """Rank `rank`'s part [b, e) of the frame's sample range [begin, end) (rt_multi.cpp shard_render)."""
     n = end - begin
     return begin + n * rank // world, begin + n * (rank + 1) // world
 

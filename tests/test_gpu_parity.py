@@ -643,7 +643,7 @@ def test_final_scene_on_the_narrow_block(gpu, monkeypatch):
 @pytest.mark.parametrize("name,width,aspect", [("random", 48, "std16x9"), ("cornell", 40, "square"),
                                                ("earth", 48, "square"), ("final:6:60", 40, "square")])
 def test_lds_material_tables_change_nothing(gpu, monkeypatch, name, width, aspect):
-    """The scene-in-LDS block keeps the material and texture tables in LDS after the Perlin tables (rt_api.cpp
+    """The scene-in-LDS block keeps the material and texture tables in LDS after the Perlin tables (scene_compile.cpp
     n_lds_mats): the frame is the one the global-memory tables give (SHIRLEY_NO_LDS_MATS, read
     at upload), bit for bit."""
     spp = 4
@@ -663,7 +663,7 @@ def test_lds_material_tables_change_nothing(gpu, monkeypatch, name, width, aspec
 @pytest.mark.parametrize("name,width,aspect", [("random", 48, "std16x9"), ("cornell", 40, "square"),
                                                ("box-light", 48, "std16x9"), ("spheres", 48, "std16x9")])
 def test_collapse_choice_changes_nothing(gpu, monkeypatch, name, width, aspect):
-    """The 4-wide collapse is picked per scene at upload (rt_api.cpp rt_scene_upload: the optimal collapse for
+    """The 4-wide collapse is picked per scene at upload (scene_compile.cpp compile_scene: the optimal collapse for
     scene-in-LDS reference scenes, greedy otherwise).  The tree only orders and culls the
     node tests — every leaf test stays exact — so the optimal, the greedy and the automatic choice give the
     same frame, bit for bit, and that frame is the oracle's within the parity gate."""

@@ -4,7 +4,7 @@ The reference accepts a hit at t == the running closest t (sphere.rs:40-45 rejec
 rect.rs:58 only `t > t_max`), so the tied primitive tested LAST wins — provided its bounding box passes
 `hit2` (aabb.rs:62-79), whose `t_max <= t_min` test is strict, at t_max = the tie.  bbox_tree.rs:56-91
 pops rhs before lhs, so the last one tested is the leftmost leaf of the reference tree whose box passes.
-The device numbers its primitives in that leaf order (rt_api.cpp reference_ranks) and compares two tested
+The device numbers its primitives in that leaf order (scene_compile.cpp reference_ranks) and compares two tested
 candidates at an equal t by it (rt_device.h tie_takes); a traversal that skipped a box failing at the
 closest t by no more than rounding re-decides the winner once at its end from all tied primitives
 (resolve_ties; the rule is pinned on CPU in test_tie_rule.py) — whatever tree it traverses (SAH by

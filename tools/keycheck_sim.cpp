@@ -12,7 +12,7 @@
 // " pairing=ok" while every rank's sequence of issued collectives (all-gathers G, frame collectives F) is a
 // prefix of another's — RCCL then pairs like with like, and a rank that is behind only stalls its peers —,
 // else " pairing=mismatch" (a G paired with an F: undefined).
-// The simulation mirrors check_call_key and rt_render_sharded in rt_api.cpp: poisoned communicator, deferred
+// The simulation mirrors check_call_key and rt_render_sharded in rt_multi.cpp: poisoned communicator, deferred
 // check, then the gather, then the immediate check when key_check_now says so, then the frame.
 #include <cstdio>
 #include <cstdlib>

@@ -1,16 +1,17 @@
 // host_check.cpp — ASan/UBSan driver for the CPU side of the boundary: the C++ host
-// layer (serde-JSON SceneBuilder loader/saver, scenes, finalize, camera, PNG), the BVH builders of
-// libshirley_rt (bvh_build.cpp) and the C oracle, compiled from their sources with
-// -fsanitize=address,undefined (tools/sanitize/Makefile).  No GPU code is involved.
+// layer (serde-JSON SceneBuilder loader/saver, scenes, finalize, camera, PNG), the BVH builders and the
+// scene compilation of libshirley_rt (bvh_build.cpp, scene_compile.cpp) and the C oracle, compiled from
+// their sources with -fsanitize=address,undefined (tools/sanitize/Makefile).  No GPU code is involved.
 //
 //   1. every builtin scene: build -> to_json -> from_json -> to_json (byte-equal round trip) ->
-//      finalize -> both BVH builders over the objects' bounding boxes -> oracle scene -> a tiny
-//      render + tonemap -> PNG;
+//      finalize -> both BVH builders over the objects' bounding boxes -> compile_scene (validation,
+//      trees, device tables, placement plan) -> oracle scene -> a tiny render + tonemap -> PNG;
 //   2. a mutation fuzzer over the scenes' JSON (the input `ray-cli render saved` parses, reference
 //      scenes.rs:128-134): byte flips, JSON-significant insertions, deletions, duplications,
 //      truncations, extreme numbers, deep nesting, escapes.  Each mutant goes through from_json and,
-//      when it parses, finalize + the builders + a 4x3 oracle render.  Errors are expected; crashes,
-//      leaks and undefined behaviour are not (the sanitizers abort the run).
+//      when it parses, finalize + the builders + compile_scene + a 4x3 oracle render.  Errors are
+//      expected (compile_scene: RT_OK, RT_E_INVALID or RT_E_UNSUPPORTED); crashes, leaks and undefined
+//      behaviour are not (the sanitizers abort the run).
 //
 // usage: host_check <asset_dir> <n_mutants> [seed]
 #include <cinttypes>
@@ -24,6 +25,7 @@
 #include "../../include/shirley_host.h"
 #include "../../oracle/oracle.h"
 #include "../../shirley-raytracing-rs_amd/csrc/rt/bvh_build.h"
+#include "../../shirley-raytracing-rs_amd/csrc/rt/scene_compile.h"
 
 namespace {
 
@@ -81,6 +83,15 @@ int exercise(const sh_scene* s, uint64_t seed, int w, int spp, bool big_ok) {
   (void)rt::tree_branch_depth(sah);
   (void)rt::tree_branch_depth(sweep);
   int rc = 0;
+  // scene compilation as rt_scene_upload runs it: a clean status whatever the scene holds
+  for (int32_t builder : {(int32_t)RT_BVH_REFERENCE, (int32_t)RT_BVH_SAH, (int32_t)(RT_BVH_SAH | RT_BVH_NODES_LDS)}) {
+    rt::CompiledScene cs;
+    std::string err;
+    const int st = rt::compile_scene(v, builder, rt::SceneTuning{}, &cs, &err);
+    CHECK(st == RT_OK || st == RT_E_INVALID || st == RT_E_UNSUPPORTED, "compile_scene: status %d (%s)", st, err.c_str());
+    CHECK(st == RT_OK || !err.empty(), "compile_scene: status %d without a message", st);
+    if (big_ok) CHECK(st == RT_OK, "compile_scene: builtin refused: %s", err.c_str());
+  }
   if (big_ok || v->n_objects <= 4000) {
     or_scene* os = or_scene_new(v);
     if (!os) {
