@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define RT_ABI_VERSION 7
+#define RT_ABI_VERSION 8
 
 typedef enum rt_status {
   RT_OK = 0,
@@ -405,6 +405,56 @@ int rt_tonemap(const double* accum, int32_t width, int32_t height, int32_t sampl
  * row 0 = top, on `stream` (NULL: the context's stream), asynchronous.  Bit-identical to rt_tonemap. */
 int rt_tonemap_device(rt_ctx* ctx, const double* accum_dev, int32_t width, int32_t height, int32_t samples,
                       uint8_t* rgb8_dev, void* stream);
+
+/* ---- adaptive sampling (ABI 8) -------------------------------------------------
+ * One frame in steps: every pixel gets min_samples, then steps of `step` more samples go only to the
+ * 8x8 tiles whose noise estimate is still above the threshold, up to params->samples per pixel.  The
+ * counter RNG is keyed by the global (pixel, sample), so a pixel that stops after n samples holds exactly
+ * samples [0, n) of the uniform frame: its sums equal rt_render's over sample range [0, n) with the same
+ * sample_chunk bit for bit.
+ *
+ * A batch is params->sample_chunk consecutive samples of a pixel (b; 0 means 4) and y = (r + g) + b of a
+ * batch's sum one observation; a pixel's moments are m1 = sum y, m2 = sum y^2 over its n batches.  A
+ * tile's error over its K in-image pixels after N = n b samples per pixel:
+ *   v_p = max(0, m2_p - m1_p^2 / n) / (n - 1),  E = sum_p v_p,  M = sum_p m1_p,
+ *   e = sqrt(n E / K) / (M / K + N noise_floor)        (e = 0 when E == 0)
+ * — the RMS standard error of the tile's pixel means relative to the tile's mean r + g + b.  After each
+ * step a tile goes on while !(e <= threshold): a NaN error keeps rendering.  Threshold 0 stops no tile (also
+ * none with e == 0), so that frame is rt_render's; +inf stops every tile with a finite error at min_samples. */
+typedef struct rt_adaptive_params {
+  int32_t min_samples;   /* every pixel gets these first; a multiple of the batch, >= 2 batches */
+  int32_t step;          /* samples per later step; a multiple of the batch */
+  double  threshold;     /* a tile stops when its error e <= threshold; 0 = never, +inf = at min_samples */
+  double  noise_floor;   /* per-sample r+g+b added to the tile mean in e's denominator */
+} rt_adaptive_params;
+
+typedef struct rt_adaptive_report {
+  int32_t  steps, tiles, tiles_converged, pad; /* steps run; tiles of the frame; tiles the rule stopped */
+  uint64_t samples, segments;      /* paths and segments traced, summed over the steps */
+  double   kernel_ms, fold_ms;     /* device time of the trace launches / of the rest (fold kernels), summed */
+} rt_adaptive_report;
+
+/* Whole frame, blocking.  params->samples is the per-pixel maximum; samples, min_samples and step must be
+ * multiples of the batch; sample_begin, sample_count must be 0 and tile_world 1 (RT_E_INVALID otherwise).
+ * The megakernel renders the steps' tile lists: RT_ENGINE_AUTO resolves to it, RT_ENGINE_WAVEFRONT and
+ * RT_ENGINE_SPLIT return RT_E_UNSUPPORTED.  scratch_mb bounds each step's partial sums as in rt_render; the
+ * frame is bit-identical for every bound.  max_depth == 0 gives zero sums and every tile stops at
+ * min_samples.  Not available through the multi-GPU entry points; adaptive frames are not checkpointed. */
+int rt_render_adaptive(rt_ctx* ctx, const rt_camera* cam, const rt_render_params* params,
+                       const rt_adaptive_params* adaptive,
+                       double* accum_host,      /* [H][W][3] sums over each pixel's own samples, row 0 = bottom */
+                       int32_t* counts_host,    /* [H][W] samples the pixel received */
+                       double* moments_host,    /* [H][W][2] m1, m2; may be NULL */
+                       double* tile_error_host, /* [tiles] e at the tile's last check, tile k = 8x8 tile
+                                                   (k % tiles_x, k / tiles_x) from the bottom row; may be NULL */
+                       rt_adaptive_report* report /* may be NULL */);
+
+/* rt_tonemap with each pixel's own count in place of `samples` (counts: [H][W], accum's row order); a count
+ * of 0 gives black.  Uniform counts give rt_tonemap's bytes.  The device variant is asynchronous on `stream`
+ * (NULL: the context's stream) and bit-identical to the host one. */
+int rt_tonemap_counts(const double* accum, const int32_t* counts, int32_t width, int32_t height, uint8_t* rgb8);
+int rt_tonemap_counts_device(rt_ctx* ctx, const double* accum_dev, const int32_t* counts_dev, int32_t width,
+                             int32_t height, uint8_t* rgb8_dev, void* stream);
 
 #ifdef __cplusplus
 }

@@ -15,7 +15,10 @@
 // --partition tiles|samples (how --gpus splits the frame, RT_PARTITION_*; default: the library's),
 // --progressive K (the frame's samples in K consecutive ranges, rt_render_params.sample_begin / count;
 // after each range the running sums go to --dump-accum FILE + FILE.json and the PNG shows the samples so
-// far: a checkpoint), --resume FILE (continue from such a checkpoint: its sums cover samples [0, N)).
+// far: a checkpoint), --resume FILE (continue from such a checkpoint: its sums cover samples [0, N)),
+// --adaptive T (adaptive sampling, rt_render_adaptive: -s is the per-pixel maximum, an 8x8 tile stops when
+// its relative error is <= T; --min-samples N and --adaptive-step N, multiples of --sample-chunk (0 = 4),
+// --noise-floor F; the picture divides every pixel by its own sample count; one GPU, no checkpoints).
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -40,6 +43,9 @@ struct Args {
   int partition = RT_PARTITION_AUTO;
   int progressive = 1;
   std::string resume;
+  bool adaptive = false;
+  double adaptive_threshold = 0.0, noise_floor = 0.01;
+  int min_samples = 16, adaptive_step = 16;
   double fov = 20.0, focal = 1.0, aperture = 0.001;
   bool night = false, single_threaded = false;
   unsigned long long seed = 0x5EED;
@@ -54,7 +60,8 @@ struct Args {
                "         --camera-aperture F --camera-aspect-ratio std3x2|std16x9|std16x10|square|target-iphone\n"
                "         --night --scene-output FILE (random)  <scene_input> (saved)  --side-len N (spheres)\n"
                "         --seed N --device N --gpus N --partition tiles|samples --bvh reference|sah --sample-chunk N\n"
-               "         --dump-accum FILE --progressive K --resume FILE\n");
+               "         --dump-accum FILE --progressive K --resume FILE\n"
+               "         --adaptive T --min-samples N --adaptive-step N --noise-floor F\n");
   std::exit(2);
 }
 
@@ -230,7 +237,27 @@ int render_scene(const Args& a, const rt_scene_desc* desc, const rt_camera& cam)
   std::vector<double> accum;
   std::vector<uint8_t> rgb(n);
   auto t1 = std::chrono::steady_clock::now();
-  if (a.progressive > 1 || !a.resume.empty()) {
+  if (a.adaptive) {
+    // adaptive sampling: tiles stop at their own sample count, the picture divides by the counts
+    rt_adaptive_params ap{};
+    ap.min_samples = a.min_samples;
+    ap.step = a.adaptive_step;
+    ap.threshold = a.adaptive_threshold;
+    ap.noise_floor = a.noise_floor;
+    accum.resize(n);
+    std::vector<int32_t> counts(n / 3);
+    rt_adaptive_report rep{};
+    if ((st = rt_render_adaptive(ctx, &cam, &p, &ap, accum.data(), counts.data(), nullptr, nullptr, &rep))) {
+      std::fprintf(stderr, "error: %s\n", rt_last_error(ctx));
+      rt_destroy(ctx);
+      return 1;
+    }
+    rt_tonemap_counts(accum.data(), counts.data(), cam.image_width, cam.image_height, rgb.data());
+    if (verbose >= 1)
+      std::fprintf(stderr, "INFO adaptive: %d steps, mean %.2f spp of at most %d, %.1f %% of %d tiles converged\n",
+                   rep.steps, (double)rep.samples / (double)(n / 3), samples,
+                   100.0 * rep.tiles_converged / (double)(rep.tiles ? rep.tiles : 1), rep.tiles);
+  } else if (a.progressive > 1 || !a.resume.empty()) {
     // progressive rendering with checkpoints: sample ranges [b_k, b_k+1) of the frame; the host adds each
     // range's sums to the running sums in range order (so a resumed run adds exactly what an
     // uninterrupted one does) and writes the checkpoint after every range
@@ -324,7 +351,7 @@ int render_scene(const Args& a, const rt_scene_desc* desc, const rt_camera& cam)
   rt_counters_get(ctx, &cnt);
   double ms = std::chrono::duration<double, std::milli>(t2 - t1).count();
   double msamp = (double)cam.image_width * cam.image_height * samples / (cnt.kernel_ms * 1e3);
-  if (verbose >= 1)
+  if (verbose >= 1 && !a.adaptive)  // (an adaptive frame printed its own line: the counters hold its last step)
     std::fprintf(stderr,
                  "INFO upload %.1f ms, render %.1f ms (kernel %.2f ms, reduce %.3f ms): %.1f Msamples/s, %.3f segments/sample\n",
                  std::chrono::duration<double, std::milli>(t1 - t0).count(), ms, cnt.kernel_ms, cnt.reduce_ms, msamp,
@@ -370,6 +397,10 @@ int main(int argc, char** argv) {
     else if (s == "--sample-chunk") a.sample_chunk = std::atoi(next().c_str());
     else if (s == "--progressive") a.progressive = std::atoi(next().c_str());
     else if (s == "--resume") a.resume = next();
+    else if (s == "--adaptive") { a.adaptive = true; a.adaptive_threshold = std::atof(next().c_str()); }
+    else if (s == "--min-samples") a.min_samples = std::atoi(next().c_str());
+    else if (s == "--adaptive-step") a.adaptive_step = std::atoi(next().c_str());
+    else if (s == "--noise-floor") a.noise_floor = std::atof(next().c_str());
     else if (s == "--partition") {
       const std::string v = next();
       if (v == "tiles") a.partition = RT_PARTITION_TILES;
@@ -393,6 +424,10 @@ int main(int argc, char** argv) {
   if (a.gpus < 1 || a.gpus > 64) usage("--gpus must be in [1, 64]");
   if (a.progressive < 1) usage("--progressive must be >= 1");
   if (a.gpus > 1 && (a.progressive > 1 || !a.resume.empty())) usage("--progressive / --resume render on one GPU");
+
+  if (a.adaptive && (a.gpus > 1 || a.progressive > 1 || !a.resume.empty()))
+    usage("--adaptive renders on one GPU, without --progressive / --resume");
+  if (a.adaptive && !a.dump_accum.empty()) usage("--adaptive frames are not checkpointed (--dump-accum)");
 
   sh_scene* scene = nullptr;
   std::string cam_scene = a.scene;

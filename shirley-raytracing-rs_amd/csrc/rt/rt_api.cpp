@@ -11,6 +11,7 @@
 #include <string>
 #include <vector>
 
+#include "adaptive.h"
 #include "plan.h"
 #include "rt_ctx.h"
 
@@ -275,14 +276,20 @@ int resolve_range(rt_ctx* c, const rt_render_params* p, SampleRange* r) {
 // (packed=1) or rows [row0, row1).  The call's work units (pixel x chunk of samples) are traced in
 // sample passes of at most `scratch` bytes of partial sums each; every pass's reduce continues the
 // per-pixel chunk-order sums of the passes before it (reduce_kernel `accumulate`), so the frame is the
-// same for any number of passes.
+// same for any number of passes.  `step` (an adaptive step, rt_ctx.h): the listed tiles of the whole frame
+// on the megakernel, folded into out_dev and the moments by fold_stats_kernel.
 int render_window(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, const SampleRange& R, int ty0, int ty1,
-                  int row0, int row1, int packed, double* out_dev, hipStream_t s) {
+                  int row0, int row1, int packed, double* out_dev, hipStream_t s, const TileStep* step) {
   int st = check_render_args(c, cam, p);
   if (st) return st;
   HIP_TRY(c, hipSetDevice(c->device));
   const int count = R.end - R.begin;
   Layout L = layout(cam, ty0, ty1, p->tile_rank, p->tile_world);
+  if (step) {
+    if (ty0 != 0 || packed || p->tile_world != 1 || step->n_list < 1 || step->n_list > L.n_tiles)
+      return fail(c, RT_E_INVALID, "bad adaptive step");
+    L.n_tiles_rank = step->n_list;
+  }
   const long long n_pix = (long long)L.n_tiles_rank * kTilePixels;
 
   int engine = p->engine & 0xf;
@@ -291,6 +298,8 @@ int render_window(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, co
   if (engine != RT_ENGINE_MEGAKERNEL && engine != RT_ENGINE_WAVEFRONT && engine != RT_ENGINE_SPLIT)
     return fail(c, RT_E_INVALID, "bad engine %d", p->engine);
   if (engine == RT_ENGINE_SPLIT && c->split_nt == 0) engine = RT_ENGINE_MEGAKERNEL;  // scene not eligible
+  if (step && engine != RT_ENGINE_MEGAKERNEL)
+    return fail(c, RT_E_UNSUPPORTED, "tile lists are rendered by the megakernel only (engine %d)", engine);
 
   const long long lanes = (long long)c->cu_count * std::max(1, c->blocks_per_cu) * c->place.mk_threads;
   long long budget = (long long)(p->scratch_mb > 0 ? p->scratch_mb : kDefaultScratchMiB) << 20;
@@ -337,6 +346,7 @@ int render_window(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, co
   kp.work.max_depth = p->max_depth;
   kp.work.seed = p->seed;
   kp.work.div_tiles_x = make_udiv((uint32_t)L.tiles_x);
+  kp.work.tile_list = step ? step->list_dev : nullptr;
   kp.partial = static_cast<double*>(c->partial.p);
   kp.counters = static_cast<DCounters*>(c->counters.p);
 
@@ -373,6 +383,7 @@ int render_window(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, co
   for (double& x : c->lap_ms) x = 0.0;
   HIP_TRY(c, hipEventRecord(c->ev[0], s));
   const bool trace = n_pix > 0 && count > 0 && p->max_depth > 0;
+  if (step && (!trace || chunk != step->batch)) return fail(c, RT_E_INVALID, "bad adaptive step");
   if (!trace) {
     // nothing to trace: ray_color's loop never runs with max_depth == 0 (render.rs:30: every sample is
     // black), or the range is empty.  The window is written by a reduce over no chunks (zeros); the
@@ -434,8 +445,13 @@ int render_window(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, co
     }
     HIP_TRY(c, hipEventRecord(c->pass_ev[2 * k + 1], s));
     if (k == passes - 1) HIP_TRY(c, hipEventRecord(c->ev[1], s));
-    HIP_TRY(c, launch_reduce(kp.partial, w.n_chunks, L.n_tiles_rank, L.tiles_x, ty0, p->tile_rank, p->tile_world,
-                             cam->image_width, row0, row1, packed, k > 0 ? 1 : 0, out_dev, s));
+    if (step)
+      HIP_TRY(c, launch_fold_stats(kp.partial, w.n_chunks, step->n_list, step->list_dev, L.tiles_x, cam->image_width,
+                                   cam->image_height, step->batches_before + c1, step->batch, step->noise_floor,
+                                   out_dev, step->moments_dev, step->err_dev, s));
+    else
+      HIP_TRY(c, launch_reduce(kp.partial, w.n_chunks, L.n_tiles_rank, L.tiles_x, ty0, p->tile_rank, p->tile_world,
+                               cam->image_width, row0, row1, packed, k > 0 ? 1 : 0, out_dev, s));
     c->last_passes = k + 1;
   }
   HIP_TRY(c, hipEventRecord(c->ev[2], s));
@@ -490,7 +506,7 @@ int rt_destroy(rt_ctx* c) {
   if (!c) return RT_OK;
   (void)hipSetDevice(c->device);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
-  for (DevBuf* b : {&c->nodes, &c->nodes4, &c->prims, &c->mats, &c->texs, &c->perlin, &c->texels, &c->exts, &c->partial, &c->kcam, &c->shutter0,
+  for (DevBuf* b : {&c->nodes, &c->nodes4, &c->prims, &c->mats, &c->texs, &c->perlin, &c->texels, &c->exts, &c->partial, &c->kcam, &c->shutter0, &c->moments, &c->tile_list, &c->tile_err,
                     &c->accum, &c->counters, &c->unit_counter, &c->wf_pool, &c->wf_iters, &c->packed, &c->gathered,
                     &c->parts, &c->band, &c->digests})
     release(*b);
@@ -866,6 +882,132 @@ int rt_tonemap_device(rt_ctx* c, const double* accum_dev, int32_t width, int32_t
   const double inv = 1.0 / (double)(samples == 0 ? 1 : samples);
   HIP_TRY(c, launch_tonemap(accum_dev, width, height, inv, rgb8_dev, s));
   return RT_OK;
+}
+
+int rt_tonemap_counts(const double* accum, const int32_t* counts, int32_t width, int32_t height, uint8_t* rgb8) {
+  if (!accum || !counts || !rgb8 || width < 1 || height < 1) return RT_E_INVALID;
+  for (int32_t j = 0; j < height; ++j)
+    for (int32_t i = 0; i < width; ++i) {
+      const double* c = accum + ((size_t)j * width + i) * 3;
+      uint8_t* o = rgb8 + ((size_t)(height - j - 1) * width + i) * 3;
+      const int32_t n = counts[(size_t)j * width + i];
+      const double inv = n > 0 ? 1.0 / (double)n : 0.0;
+      for (int k = 0; k < 3; ++k) {
+        double y = std::sqrt(c[k] * inv) * 255.999;  // rt_tonemap's arithmetic on the pixel's own count
+        o[k] = (n <= 0 || std::isnan(y) || y <= 0.0) ? 0 : (y >= 255.0 ? 255 : (uint8_t)y);
+      }
+    }
+  return RT_OK;
+}
+
+int rt_tonemap_counts_device(rt_ctx* c, const double* accum_dev, const int32_t* counts_dev, int32_t width,
+                             int32_t height, uint8_t* rgb8_dev, void* stream) {
+  if (!c || !accum_dev || !counts_dev || !rgb8_dev || width < 1 || height < 1) return RT_E_INVALID;
+  hipStream_t s;
+  resolve_stream(c, stream, &s);
+  HIP_TRY(c, hipSetDevice(c->device));
+  HIP_TRY(c, launch_tonemap_counts(accum_dev, counts_dev, width, height, rgb8_dev, s));
+  return RT_OK;
+}
+
+// The step loop of an adaptive frame (adaptive.h) on the host, like the traversal stacks' sizing: after
+// each step the listed tiles' errors come back, the tiles that go on make the next (sorted) list — one
+// small round trip per step, a deterministic list and no device compaction.
+int rt_render_adaptive(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, const rt_adaptive_params* a,
+                       double* accum_host, int32_t* counts_host, double* moments_host, double* tile_error_host,
+                       rt_adaptive_report* report) {
+  if (!c) return RT_E_INVALID;
+  if (!cam || !p || !a || !accum_host || !counts_host) return fail(c, RT_E_INVALID, "NULL argument");
+  int st = check_render_args(c, cam, p);
+  if (st) return st;
+  AdaptivePlan plan;
+  if (const char* why = adaptive_validate(p, a, &plan)) return fail(c, RT_E_INVALID, "rt_render_adaptive: %s", why);
+  const int engine = p->engine & 0xf;
+  if (engine == RT_ENGINE_WAVEFRONT || engine == RT_ENGINE_SPLIT)
+    return fail(c, RT_E_UNSUPPORTED, "rt_render_adaptive: tile lists are rendered by the megakernel only (engine %d)", engine);
+  if (engine != RT_ENGINE_AUTO && engine != RT_ENGINE_MEGAKERNEL) return fail(c, RT_E_INVALID, "bad engine %d", p->engine);
+
+  const int W = cam->image_width, H = cam->image_height;
+  const int tiles_x = (W + kTile - 1) / kTile, tiles_y = (H + kTile - 1) / kTile, n_tiles = tiles_x * tiles_y;
+  const size_t n_px = (size_t)W * H;
+  rt_adaptive_report rep{};
+  rep.tiles = n_tiles;
+  std::vector<int32_t> tile_count(n_tiles, 0);
+  std::vector<double> tile_err(n_tiles, std::numeric_limits<double>::quiet_NaN());
+  auto finish = [&]() {
+    for (int j = 0; j < H; ++j)
+      for (int i = 0; i < W; ++i) counts_host[(size_t)j * W + i] = tile_count[(j / kTile) * tiles_x + i / kTile];
+    for (int t = 0; t < n_tiles; ++t) rep.tiles_converged += tile_continues(tile_err[t], plan.threshold) ? 0 : 1;
+    if (tile_error_host) std::copy(tile_err.begin(), tile_err.end(), tile_error_host);
+    if (report) *report = rep;
+    return RT_OK;
+  };
+  if (p->max_depth == 0) {
+    // ray_color's loop never runs (render.rs:30): every sample is black and there is nothing to estimate,
+    // so every tile stops after the first step (whatever the threshold)
+    std::fill(accum_host, accum_host + n_px * 3, 0.0);
+    if (moments_host) std::fill(moments_host, moments_host + n_px * 2, 0.0);
+    std::fill(tile_count.begin(), tile_count.end(), plan.min_samples);
+    std::fill(tile_err.begin(), tile_err.end(), 0.0);
+    rep.steps = 1;
+    rep.samples = (uint64_t)n_px * (uint64_t)plan.min_samples;
+    finish();
+    if (report) report->tiles_converged = n_tiles;
+    return RT_OK;
+  }
+
+  HIP_TRY(c, hipSetDevice(c->device));
+  hipStream_t s = c->stream;
+  if ((st = ensure(c, c->accum, n_px * 3 * sizeof(double))) || (st = ensure(c, c->moments, n_px * 2 * sizeof(double))) ||
+      (st = ensure(c, c->tile_list, (size_t)n_tiles * sizeof(uint32_t))) ||
+      (st = ensure(c, c->tile_err, (size_t)n_tiles * sizeof(double))))
+    return st;
+  HIP_TRY(c, hipMemsetAsync(c->accum.p, 0, n_px * 3 * sizeof(double), s));
+  HIP_TRY(c, hipMemsetAsync(c->moments.p, 0, n_px * 2 * sizeof(double), s));
+
+  rt_render_params q = *p;
+  q.sample_chunk = plan.batch;
+  q.engine = RT_ENGINE_MEGAKERNEL | (p->engine & RT_ENGINE_TIMING);
+  std::vector<uint32_t> list(n_tiles);
+  for (int t = 0; t < n_tiles; ++t) list[t] = (uint32_t)t;
+  std::vector<double> err(n_tiles);
+  const int n_steps = adaptive_n_steps(plan);
+  for (int k = 0; k < n_steps && !list.empty(); ++k) {
+    SampleRange R;
+    adaptive_step_range(plan, k, &R.begin, &R.end);
+    if (R.end <= R.begin) break;
+    const size_t n_list = list.size();
+    HIP_TRY(c, hipMemcpyAsync(c->tile_list.p, list.data(), n_list * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    TileStep ts{};
+    ts.list_dev = static_cast<const uint32_t*>(c->tile_list.p);
+    ts.n_list = (int)n_list;
+    ts.moments_dev = static_cast<double*>(c->moments.p);
+    ts.err_dev = static_cast<double*>(c->tile_err.p);
+    ts.batches_before = R.begin / plan.batch;
+    ts.batch = plan.batch;
+    ts.noise_floor = plan.noise_floor;
+    st = render_window(c, cam, &q, R, 0, tiles_y, 0, H, 0, static_cast<double*>(c->accum.p), s, &ts);
+    if (st) return st;
+    HIP_TRY(c, hipMemcpyAsync(err.data(), c->tile_err.p, n_list * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    rt_counters cnt;
+    if ((st = rt_counters_get(c, &cnt))) return st;
+    rep.steps += 1;
+    rep.samples += cnt.samples;
+    rep.segments += cnt.segments;
+    rep.kernel_ms += cnt.kernel_ms;
+    rep.fold_ms += cnt.reduce_ms;
+    for (size_t i = 0; i < n_list; ++i) {
+      tile_err[list[i]] = err[i];
+      tile_count[list[i]] = R.end;
+    }
+    list.resize(adaptive_compact(list.data(), err.data(), n_list, plan.threshold, list.data()));
+  }
+  HIP_TRY(c, hipMemcpyAsync(accum_host, c->accum.p, n_px * 3 * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (moments_host)
+    HIP_TRY(c, hipMemcpyAsync(moments_host, c->moments.p, n_px * 2 * sizeof(double), hipMemcpyDeviceToHost, s));
+  HIP_TRY(c, hipStreamSynchronize(s));
+  return finish();
 }
 
 }  // extern "C"

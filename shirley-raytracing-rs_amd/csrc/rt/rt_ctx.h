@@ -59,6 +59,7 @@ struct rt_ctx {
   int n_perlin = 0;
   // per-render scratch
   DevBuf partial, accum, counters, unit_counter, kcam;
+  DevBuf moments, tile_list, tile_err;  // rt_render_adaptive: [H][W][2] moments, a step's tile list and its errors
   DevBuf shutter0;  // {0, 0}: the shutter of rt_scene_hit / rt_probe_segment queries (DScene.shutter)
   DevBuf wf_pool, wf_iters;          // path slots (SoA) + texture queue; per-iteration counters ring
   uint32_t* wf_host = nullptr;       // pinned readback of the retired-slot count, one word per batch
@@ -132,10 +133,23 @@ struct SampleRange {
   int begin = 0, end = 0;
 };
 
+// An adaptive step (rt_render_adaptive) as render_window runs it: the megakernel renders the listed tiles
+// (DWork.tile_list) and fold_stats_kernel takes the reduce's place — out_dev is the whole frame's [H][W][3]
+// sums, continued in chunk order like a later sample pass; one chunk is one batch.
+struct TileStep {
+  const uint32_t* list_dev;  // ascending global tile indices (device)
+  int n_list;
+  double* moments_dev;       // [H][W][2]
+  double* err_dev;           // [n_list]: the listed tiles' errors after the step
+  long long batches_before;  // batches every listed pixel holds before the step
+  int batch;                 // samples per batch (the step's unit length)
+  double noise_floor;
+};
+
 // rt_api.cpp
 int check_render_args(rt_ctx* c, const rt_camera* cam, const rt_render_params* p);
 int resolve_range(rt_ctx* c, const rt_render_params* p, SampleRange* r);
 int render_window(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, const SampleRange& R, int ty0, int ty1,
-                  int row0, int row1, int packed, double* out_dev, hipStream_t s);
+                  int row0, int row1, int packed, double* out_dev, hipStream_t s, const TileStep* step = nullptr);
 
 }  // namespace rt

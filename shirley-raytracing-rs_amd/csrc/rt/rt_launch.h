@@ -21,6 +21,11 @@ void timeline_dump();
 hipError_t launch_reduce(const double* partial, int n_chunks, int n_tiles_rank, int tiles_x, int ty0, int tile_rank,
                          int tile_world, int width, int row0, int row1, int packed, int accumulate, double* out,
                          hipStream_t stream);
+hipError_t launch_fold_stats(const double* partial, int n_chunks, int n_list, const uint32_t* tile_list, int tiles_x,
+                             int width, int height, long long n_batches, int batch, double noise_floor,
+                             double* accum, double* moments, double* err, hipStream_t stream);
+hipError_t launch_tonemap_counts(const double* accum, const int32_t* counts, int width, int height, uint8_t* rgb8,
+                                 hipStream_t stream);
 hipError_t launch_tonemap(const double* accum, int width, int height, double inv, uint8_t* rgb8, hipStream_t stream);
 hipError_t launch_unpack(const double* gathered, int world, int max_tiles, int n_tiles_total, int tiles_x, int width,
                          int height, double* out, hipStream_t stream);

@@ -241,6 +241,11 @@ struct DWork {
   uint32_t seg_len, n_segs;
   // shared queue (n_segs == 0): units a wave takes per atomic (plan.h)
   uint32_t q_window, pad_q;
+  // megakernel only (adaptive steps, adaptive.h): when not null, the launch renders the tiles
+  // tile_list[0 .. n_tiles_rank) — global tile indices over the whole frame's tile grid, ascending —
+  // instead of the tiles k % tile_world == tile_rank; ty0 is 0 then.  Device memory.  Read by the
+  // trace_kernel<.., LIST = true> instances only (launch_trace picks them when it is set).
+  const uint32_t* tile_list;
 };
 
 // Statistics counters, kCounterSlots copies one 128-B line apart: a block adds into slot

@@ -17,6 +17,7 @@
 //   * Perlin marble octaves and rejection-sampling attempts of a segment are dealt across the whole
 //     wave (marble_coop, random_in_unit_sphere_coop);
 //   * per-unit partial sums go to HBM once; a reduce kernel sums chunks in order (deterministic).
+#include "adaptive.h"
 #include "rt_device.h"
 #include "rt_launch.h"
 
@@ -56,7 +57,9 @@ constexpr int kNarrowWaves = RT_NARROW_WAVES;
 #define RT_NARROW_WAVES_EXT 3
 #endif
 
-template <int THREADS, int MODE, bool EXT>
+// LIST: the launch's tiles come from DWork.tile_list (an adaptive step, adaptive.h) — separate instances, so
+// that every other call runs the code it ran without the list.
+template <int THREADS, int MODE, bool EXT, bool LIST = false>
 __global__ __launch_bounds__(THREADS, THREADS >= kTraceThreadsWide3 ? 1 : (EXT ? RT_NARROW_WAVES_EXT : kNarrowWaves))
 void trace_kernel(KParams P) {
   extern __shared__ unsigned char lds_raw[];
@@ -275,7 +278,15 @@ void trace_kernel(KParams P) {
         KCamera* kc = &kb->cam;
         const uint32_t pt = (uint32_t)kw->n_chunks * (uint32_t)kTilePixels, i32 = (uint32_t)idx;
         const uint32_t lt = udiv(i32, UDiv{kw->div_unit_tile.m, kw->div_unit_tile.s1, kw->div_unit_tile.s2});  // i32 / pt
-        const uint32_t g32 = lt * (uint32_t)kw->tile_world + (uint32_t)kw->tile_rank;
+        uint32_t g32;
+        if constexpr (LIST) {
+          // an adaptive step's launch names its tiles in a list (DWork.tile_list, read here like the rest
+          // of the descriptor: not held across the loop)
+          typedef __attribute__((address_space(1))) const uint32_t GTile;
+          g32 = ((GTile*)kw->tile_list)[lt];
+        } else {
+          g32 = lt * (uint32_t)kw->tile_world + (uint32_t)kw->tile_rank;
+        }
         const uint32_t y32 = udiv(g32, UDiv{kw->div_tiles_x.m, kw->div_tiles_x.s1, kw->div_tiles_x.s2});  // g32 / tiles_x
         const uint32_t rem = i32 - lt * pt;
         const int tx = (int)(g32 - y32 * (uint32_t)kw->tiles_x);
@@ -465,6 +476,82 @@ __global__ __launch_bounds__(256) void reduce_kernel(const double* __restrict__ 
     out[o + 1] = g;
     out[o + 2] = b;
   }
+}
+
+// The reduce of an adaptive step (rt_render_adaptive; adaptive.h): one wave per listed tile, one lane per
+// pixel, so a 256-thread block serves four tiles.  The partials ([n_chunks][n_list * 64][3], one chunk =
+// one batch) are read once.  Per in-image pixel, in chunk order: accum[c] += p[c] from the stored value —
+// reduce_kernel's additions with `accumulate` — and the batch observation y = (p[0] + p[1]) + p[2] goes
+// into the pixel's moments, m1 += y, m2 = fma(y, y, m2) ([H][W][2] f64).  Then the tile's error after
+// n_batches batches per pixel: the lanes' variances and first moments are summed over the wave by an xor
+// butterfly — offsets 32, 16, 8, 4, 2, 1, lane l adding lane l ^ offset's value to its own, so every lane
+// holds the same sum of a fixed tree (no atomics) — and lane 0 writes tile_error(...) to err[list
+// position].  Out-of-image lanes of edge tiles contribute 0 and are not counted in K.
+__global__ __launch_bounds__(256) void fold_stats_kernel(const double* __restrict__ partial, int n_chunks, int n_list,
+                                                         const uint32_t* __restrict__ tile_list, int tiles_x,
+                                                         int width, int height, long long n_batches, int batch,
+                                                         double noise_floor, double* __restrict__ accum,
+                                                         double* __restrict__ moments, double* __restrict__ err) {
+  const int lt = (int)(blockIdx.x * (blockDim.x / kWave) + threadIdx.x / kWave);  // wave-uniform
+  if (lt >= n_list) return;
+  const int lp = (int)(threadIdx.x % kWave);
+  const uint32_t g = tile_list[lt];
+  const int px = (int)(g % (uint32_t)tiles_x) * kTile + lp % kTile;
+  const int py = (int)(g / (uint32_t)tiles_x) * kTile + lp / kTile;
+  const bool inside = px < width && py < height;
+  double v = 0.0, m1 = 0.0;
+  if (inside) {
+    const long long pix = (long long)py * width + px;
+    const long long n_pix = (long long)n_list * kTilePixels, i = (long long)lt * kTilePixels + lp;
+    double r = accum[pix * 3 + 0], gr = accum[pix * 3 + 1], b = accum[pix * 3 + 2];
+    double m2 = moments[pix * 2 + 1];
+    m1 = moments[pix * 2 + 0];
+#pragma unroll 8
+    for (int c = 0; c < n_chunks; ++c) {
+      const double* p = partial + ((long long)c * n_pix + i) * 3;
+      const double p0 = p[0], p1 = p[1], p2 = p[2];
+      r += p0;
+      gr += p1;
+      b += p2;
+      const double y = (p0 + p1) + p2;
+      m1 += y;
+      m2 = fma(y, y, m2);
+    }
+    accum[pix * 3 + 0] = r;
+    accum[pix * 3 + 1] = gr;
+    accum[pix * 3 + 2] = b;
+    moments[pix * 2 + 0] = m1;
+    moments[pix * 2 + 1] = m2;
+    v = pixel_variance(m1, m2, n_batches);
+  }
+  double E = v, M = inside ? m1 : 0.0;
+  int K = inside ? 1 : 0;
+  for (int off = kWave / 2; off > 0; off >>= 1) {
+    E += __shfl_xor(E, off);
+    M += __shfl_xor(M, off);
+    K += __shfl_xor(K, off);
+  }
+  if (lp == 0) err[lt] = tile_error(E, M, K, n_batches, batch, noise_floor);
+}
+
+// rt_tonemap_counts_device: tonemap_kernel with the pixel's own sample count in place of the frame's
+// (1 / count is the host's IEEE division too); a count of 0 gives black.
+__global__ __launch_bounds__(256) void tonemap_counts_kernel(const double* __restrict__ accum,
+                                                             const int32_t* __restrict__ counts, int width, int height,
+                                                             uint8_t* __restrict__ rgb8) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long long n = (long long)width * height * 3;
+  if (i >= n) return;
+  const long long row = i / ((long long)width * 3), rest = i - row * width * 3;
+  const long long src = ((long long)(height - 1 - row) * width) * 3 + rest;
+  const int32_t cnt = counts[src / 3];
+  if (cnt <= 0) {
+    rgb8[i] = 0;
+    return;
+  }
+  const double inv = 1.0 / (double)cnt;
+  const double y = sqrt(accum[src] * inv) * 255.999;
+  rgb8[i] = (y != y || y <= 0.0) ? (uint8_t)0 : (y >= 255.0 ? (uint8_t)255 : (uint8_t)y);
 }
 
 // Sample-partitioned frames (RT_PARTITION_SAMPLES): a rank's row band holds one partial band per rank,
@@ -744,6 +831,10 @@ static hipError_t occupancy_impl1(const DScene& S, int* blocks_per_cu) {
   hipError_t e = hipFuncSetAttribute((const void*)trace_kernel<THREADS, MODE, EXT>,
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e != hipSuccess) return e;
+  // (the tile-list instance runs in the same launch shape: same block, same LDS)
+  e = hipFuncSetAttribute((const void*)trace_kernel<THREADS, MODE, EXT, true>,
+                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (e != hipSuccess) return e;
   return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, trace_kernel<THREADS, MODE, EXT>, THREADS, lds);
 }
 template <int THREADS, int MODE>
@@ -751,12 +842,19 @@ static hipError_t occupancy_impl(const DScene& S, int* blocks_per_cu) {
   return S.exts ? occupancy_impl1<THREADS, MODE, true>(S, blocks_per_cu)
                 : occupancy_impl1<THREADS, MODE, false>(S, blocks_per_cu);
 }
+template <int THREADS, int MODE, bool EXT>
+static void launch_trace2(const KParams& p, int blocks, size_t lds, hipStream_t stream) {
+  if (p.work.tile_list)
+    hipLaunchKernelGGL((trace_kernel<THREADS, MODE, EXT, true>), dim3(blocks), dim3(THREADS), lds, stream, p);
+  else
+    hipLaunchKernelGGL((trace_kernel<THREADS, MODE, EXT>), dim3(blocks), dim3(THREADS), lds, stream, p);
+}
 template <int THREADS, int MODE>
 static void launch_trace1(const KParams& p, int blocks, size_t lds, hipStream_t stream) {
   if (p.scene.exts)
-    hipLaunchKernelGGL((trace_kernel<THREADS, MODE, true>), dim3(blocks), dim3(THREADS), lds, stream, p);
+    launch_trace2<THREADS, MODE, true>(p, blocks, lds, stream);
   else
-    hipLaunchKernelGGL((trace_kernel<THREADS, MODE, false>), dim3(blocks), dim3(THREADS), lds, stream, p);
+    launch_trace2<THREADS, MODE, false>(p, blocks, lds, stream);
 }
 
 static hipError_t hit_prepare(const DScene& S) {
@@ -795,17 +893,17 @@ hipError_t launch_trace(const KParams& p, int blocks, int threads, hipStream_t s
                                      p.scene.n_lds_mats, p.scene.n_lds_texs);
   if (threads == kTraceThreadsWide && !p.scene.exts) {
     if (p.scene.n_lds_prims > 0)
-      hipLaunchKernelGGL((trace_kernel<kTraceThreadsWide, kSceneLds, false>), dim3(blocks), dim3(threads), lds, stream, p);
+      launch_trace2<kTraceThreadsWide, kSceneLds, false>(p, blocks, lds, stream);
     else
-      hipLaunchKernelGGL((trace_kernel<kTraceThreadsWide, kNodesLds, false>), dim3(blocks), dim3(threads), lds, stream, p);
+      launch_trace2<kTraceThreadsWide, kNodesLds, false>(p, blocks, lds, stream);
     return hipGetLastError();
   }
   if (threads == kTraceThreadsWide3) {
     if (!p.scene.exts) return hipErrorInvalidValue;
     if (p.scene.n_lds_prims > 0)
-      hipLaunchKernelGGL((trace_kernel<kTraceThreadsWide3, kSceneLds, true>), dim3(blocks), dim3(threads), lds, stream, p);
+      launch_trace2<kTraceThreadsWide3, kSceneLds, true>(p, blocks, lds, stream);
     else
-      hipLaunchKernelGGL((trace_kernel<kTraceThreadsWide3, kNodesLds, true>), dim3(blocks), dim3(threads), lds, stream, p);
+      launch_trace2<kTraceThreadsWide3, kNodesLds, true>(p, blocks, lds, stream);
     return hipGetLastError();
   }
   switch (node_mode4(p.scene)) {
@@ -912,6 +1010,25 @@ hipError_t launch_reduce(const double* partial, int n_chunks, int n_tiles_rank, 
   if (blocks == 0) return hipSuccess;
   hipLaunchKernelGGL(reduce_kernel, dim3(blocks), dim3(256), 0, stream, partial, n_chunks, n_tiles_rank, tiles_x,
                      ty0, tile_rank, tile_world, width, row0, row1, packed, accumulate, out);
+  return hipGetLastError();
+}
+
+hipError_t launch_fold_stats(const double* partial, int n_chunks, int n_list, const uint32_t* tile_list, int tiles_x,
+                             int width, int height, long long n_batches, int batch, double noise_floor,
+                             double* accum, double* moments, double* err, hipStream_t stream) {
+  const int blocks = (n_list + 3) / 4;  // one wave per listed tile
+  if (blocks == 0) return hipSuccess;
+  hipLaunchKernelGGL(fold_stats_kernel, dim3(blocks), dim3(256), 0, stream, partial, n_chunks, n_list, tile_list,
+                     tiles_x, width, height, n_batches, batch, noise_floor, accum, moments, err);
+  return hipGetLastError();
+}
+
+hipError_t launch_tonemap_counts(const double* accum, const int32_t* counts, int width, int height, uint8_t* rgb8,
+                                 hipStream_t stream) {
+  const long long n = (long long)width * height * 3;
+  const int blocks = (int)((n + 255) / 256);
+  if (blocks == 0) return hipSuccess;
+  hipLaunchKernelGGL(tonemap_counts_kernel, dim3(blocks), dim3(256), 0, stream, accum, counts, width, height, rgb8);
   return hipGetLastError();
 }
 

@@ -99,6 +99,17 @@ class rt_counters(C.Structure):
                 ("passes", C.c_int32), ("trace_launches", C.c_int32), ("scratch_bytes", C.c_uint64)]
 
 
+class rt_adaptive_params(C.Structure):  # ABI 8
+    _fields_ = [("min_samples", C.c_int32), ("step", C.c_int32), ("threshold", C.c_double),
+                ("noise_floor", C.c_double)]
+
+
+class rt_adaptive_report(C.Structure):  # ABI 8
+    _fields_ = [("steps", C.c_int32), ("tiles", C.c_int32), ("tiles_converged", C.c_int32), ("pad", C.c_int32),
+                ("samples", C.c_uint64), ("segments", C.c_uint64), ("kernel_ms", C.c_double),
+                ("fold_ms", C.c_double)]
+
+
 class rt_bvh_node(C.Structure):
     _fields_ = [("box", _d6), ("leaf", C.c_int32), ("lhs", C.c_int32), ("rhs", C.c_int32), ("pad", C.c_int32)]
 
@@ -162,6 +173,12 @@ RT_SIGNATURES = {
     "rt_tonemap": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "rt_tonemap_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
                                     C.c_void_p]),
+    "rt_render_adaptive": (C.c_int, [C.c_void_p, C.POINTER(rt_camera), C.POINTER(rt_render_params),
+                                     C.POINTER(rt_adaptive_params), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.POINTER(rt_adaptive_report)]),
+    "rt_tonemap_counts": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
+    "rt_tonemap_counts_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
+                                           C.c_void_p]),
 }
 
 # every symbol declared in include/shirley_host.h

@@ -51,6 +51,23 @@ class RenderSettings:
         return p
 
 
+@dataclass
+class AdaptiveSettings:
+    """rt_adaptive_params: every pixel gets `min_samples`, then steps of `step` samples go to the 8x8 tiles
+    whose error is still above `threshold` (0 = never stop, inf = stop at min_samples), up to the
+    RenderSettings' samples.  All three sample counts are multiples of the batch (sample_chunk, 0 = 4)."""
+    threshold: float = 0.05
+    min_samples: int = 16
+    step: int = 16
+    noise_floor: float = 0.01
+
+    def params(self) -> N.rt_adaptive_params:
+        a = N.rt_adaptive_params()
+        a.min_samples, a.step = int(self.min_samples), int(self.step)
+        a.threshold, a.noise_floor = float(self.threshold), float(self.noise_floor)
+        return a
+
+
 class Device:
     """One rt_ctx (one MI355X)."""
 
@@ -100,6 +117,28 @@ class Device:
         p = settings.params()
         _check(self._h, N.rt_lib().rt_render(self._h, C.byref(camera), C.byref(p), out.ctypes.data))
         return out
+
+    def render_adaptive(self, camera: N.rt_camera, settings: RenderSettings, adaptive: AdaptiveSettings):
+        """rt_render_adaptive -> (accum [H][W][3] sums over each pixel's own samples, counts [H][W] int32,
+        moments [H][W][2] (m1, m2 of the batch sums' r+g+b), tile_error [tiles_y][tiles_x], report)."""
+        h, w = camera.image_height, camera.image_width
+        accum = np.zeros((h, w, 3), dtype=np.float64)
+        counts = np.zeros((h, w), dtype=np.int32)
+        moments = np.zeros((h, w, 2), dtype=np.float64)
+        tile_error = np.zeros(((h + 7) // 8, (w + 7) // 8), dtype=np.float64)
+        report = N.rt_adaptive_report()
+        p, a = settings.params(), adaptive.params()
+        _check(self._h, N.rt_lib().rt_render_adaptive(self._h, C.byref(camera), C.byref(p), C.byref(a),
+                                                      accum.ctypes.data, counts.ctypes.data, moments.ctypes.data,
+                                                      tile_error.ctypes.data, C.byref(report)))
+        return accum, counts, moments, tile_error, report
+
+    def tonemap_counts_device(self, accum_ptr: int, counts_ptr: int, width: int, height: int, rgb8_ptr: int,
+                              stream: int = 0):
+        """rt_tonemap_counts_device: as tonemap_device with a device [H][W] int32 image of per-pixel counts."""
+        _check(self._h, N.rt_lib().rt_tonemap_counts_device(self._h, C.c_void_p(accum_ptr), C.c_void_p(counts_ptr),
+                                                            int(width), int(height), C.c_void_p(rgb8_ptr),
+                                                            C.c_void_p(stream or None)))
 
     def render_scanlines(self, camera: N.rt_camera, settings: RenderSettings, line_begin: int,
                          line_end: int) -> np.ndarray:
@@ -238,6 +277,18 @@ def to_image(accum: np.ndarray, samples: int) -> np.ndarray:
     code = N.rt_lib().rt_tonemap(a.ctypes.data, w, h, int(samples), out.ctypes.data)
     if code:
         raise N.RtError(code, "rt_tonemap failed")
+    return out
+
+
+def to_image_counts(accum: np.ndarray, counts: np.ndarray) -> np.ndarray:
+    """rt_tonemap_counts: to_image with each pixel's own sample count (an adaptive frame); count 0 -> black."""
+    h, w, _ = accum.shape
+    a = np.ascontiguousarray(accum, dtype=np.float64)
+    n = np.ascontiguousarray(counts, dtype=np.int32).reshape(h, w)
+    out = np.zeros((h, w, 3), dtype=np.uint8)
+    code = N.rt_lib().rt_tonemap_counts(a.ctypes.data, n.ctypes.data, w, h, out.ctypes.data)
+    if code:
+        raise N.RtError(code, "rt_tonemap_counts failed")
     return out
 
 
