@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define RT_ABI_VERSION 8
+#define RT_ABI_VERSION 9
 
 typedef enum rt_status {
   RT_OK = 0,
@@ -222,6 +222,9 @@ typedef struct rt_scene_stats {
   int32_t n_nodes4;     /* 4-wide f32 nodes */
   int32_t wide_block;   /* 1: the trace kernel keeps the whole 4-wide tree in LDS (1024-thread blocks) */
   double origin_limit;  /* rays with max|origin| above this take the f64 re-test of the f32 node boxes */
+  /* ABI 9 */
+  int32_t hop_pass;     /* 1: the trace kernel runs its hop pass (a reference scene held in LDS with a dielectric
+                         * RectBox; SHIRLEY_NO_HOP at upload: 0); frames and counters are the same either way */
 } rt_scene_stats;
 
 /* Counters of the last render call (deterministic for a given seed). */

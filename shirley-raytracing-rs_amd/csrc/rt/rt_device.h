@@ -1564,6 +1564,67 @@ __device__ __forceinline__ int traverse4(const DScene& S, const typename Node4Se
   return best;
 }
 
+// traverse4 for a ray whose closest hit is decided at the first node (the megakernel's hop pass, trace.hip):
+// traverse4's prologue, its first visit (node4_visit and leaf_tests4 on S.root4) and node4_next's cull of the
+// internal children — packed child word <= bits(tmaxf) | key_mask — without the sort and without stack
+// writes.  True when no internal child survives the cull, a leaf was hit and no tie is marked: traverse4
+// would then pop its empty stack and return the same best / t_best / face_best (resolve_ties does nothing
+// without the mark).  False: the outputs mean nothing and the caller runs traverse4.
+template <int MODE>
+__device__ __forceinline__ bool traverse4_root(const DScene& S, const DNode4F* lds_nodes, const DPrim* lds_prims, v3 o,
+                                               v3 d, double t_min, double& t_best, int& best, int& face_best,
+                                               const Rng& rk, uint64_t seed, unsigned& visits, unsigned& ptests) {
+  bool inv_ok;
+  const v3 inv = inv_dir(d, inv_ok);
+  const RaySigns ns = ray_signs(inv);
+  const RayF rf = ray_f<DNode4F>(S, o, inv);
+  const double a = len2(d);
+  const Recip ra = recip(a);
+  const bool ra_ok = inv_ok && a >= 0x1p-300 && a <= 0x1p300 && rf.fast && t_min >= 0.001;
+  float tmaxf = tmax_f32(t_best);
+  best = -1;
+  unsigned xdefer = 0u;
+  int4 ch;
+  float k0, k1, k2, k3;
+  const int32_t* chp;
+  const unsigned lm = node4_visit<MODE>(S, lds_nodes, o, inv, rf, t_min, t_best, tmaxf, S.root4, ch, k0, k1, k2, k3,
+                                        visits, chp);
+  if (lm)
+    leaf_tests4<MODE, false>(S, lds_prims, o, d, inv, ns, ra, ra_ok, t_min, lm, ch.x, ch.y, ch.z, ch.w, chp, t_best,
+                             tmaxf, best, face_best, rk, seed, ptests, xdefer);
+  const unsigned km = S.key_mask;
+  const unsigned p0 = (__float_as_uint(k0) & ~km) | (unsigned)ch.x, p1 = (__float_as_uint(k1) & ~km) | (unsigned)ch.y;
+  const unsigned p2 = (__float_as_uint(k2) & ~km) | (unsigned)ch.z, p3 = (__float_as_uint(k3) & ~km) | (unsigned)ch.w;
+  const unsigned lim = __float_as_uint(tmaxf) | km;
+  return min(min(p0, p1), min(p2, p3)) > lim && best >= 0 && !(best & kTieBit);
+}
+#ifdef RT_HOP_ROOT_OUTLINE
+// A/B only: traverse4_root as a call, like resolve_ties_ool — the launch-uniform scene fields
+// read back as such into a local scene record.  Headline 2880 against the inline form's 2920 Msamples/s (the
+// call's live registers: 10 spilled VGPRs and 14 spilled SGPRs against 4 and 6); not built by default.
+struct RootHit {
+  int ok, best, face;
+  double t;
+};
+template <int MODE>
+__device__ __noinline__ RootHit traverse4_root_ool(const DNode4F* lds_nodes, const DPrim* lds_prims, const DPrim* prims_v,
+                                                   int root4, unsigned key_mask, float origin_limit, v3 o, v3 d, Rng rk,
+                                                   uint64_t seed_v) {
+  DScene S{};
+  S.prims = uniform_ptr(prims_v);
+  S.root4 = __builtin_amdgcn_readfirstlane(root4);
+  S.key_mask = (unsigned)__builtin_amdgcn_readfirstlane((int)key_mask);
+  S.origin_limit = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(origin_limit)));
+  RootHit r{0, -1, -1, __builtin_inf()};
+  unsigned visits = 0, ptests = 0;
+  r.ok = traverse4_root<MODE>(S, lds_nodes, lds_prims, o, d, 0.001, r.t, r.best, r.face, rk, uniform64(seed_v), visits,
+                              ptests)
+             ? 1
+             : 0;
+  return r;
+}
+#endif
+
 // Step-wise form for wf_extend4, where a ray's traversal state lives across loop iterations.
 struct Trav4 {
   v3 inv;
@@ -2051,6 +2112,15 @@ __device__ __forceinline__ v3 draws_coop(Rng& r, uint64_t seed, int kind, bool l
   }
   return p;
 }
+// draws_coop's kDrawDiel for one lane on its own (the hop pass): the uniform of draw d — block d/2's even
+// half, or the cached odd half — and the bits of the cache after the draw, for shade_dielectric to consume.
+__device__ __forceinline__ v3 draw_diel(const Rng& r, uint64_t seed) {
+  const bool even = (r.draw & 1u) == 0u;
+  uint64_t a0 = 0, a1 = 0;
+  if (even) philox_block(seed, r.pixel, r.sample, r.draw >> 1, a0, a1);
+  const uint64_t cached = (uint64_t)r.c2 | ((uint64_t)r.c3 << 32);
+  return V(__builtin_amdgcn_ldexp(draw_bits(even ? a0 : cached), -53), u64_as_double(even ? a1 : cached), 0.0);
+}
 
 // camera/mod.rs:97-132 from the sample's draws: jitter (x, y) and the unit-disk point (lens cameras).
 // CAM: a DCamera (reference) or a pointer-like to one (the megakernel's constant-address-space copy).
@@ -2388,6 +2458,30 @@ __device__ __forceinline__ bool shade_pre(const DScene& S, const DMat& m, int le
   return true;
 }
 
+// shade_factor's dielectric branch on its own, operation for operation (dielectric.rs:21-49; the attenuation
+// is Color::ones()), for the hop pass: r = (the uniform drawn ahead, the bits of the cache after it, 0) as
+// draw_diel returns it, un = unit(d).  (A copy: shade_factor calling this changed the register assignment of
+// every megakernel instance.  Change both together: tests/test_gpu_hop.py compares frames shaded by the two.)
+__device__ __forceinline__ void shade_dielectric(const DMat& m, v3 r, v3 un, Rng& rng, v3& o, v3& d, const Hit& h) {
+  PH_COUNT(17);
+  double ratio = h.front_face ? m.inv_param : m.param;  // 1.0 / ir, precomputed
+  const v3 ud = un;
+  double cos_theta = fmin_one(dot(scale(ud, -1.0), h.normal));
+  // ratio * sin_theta > 1 (TIR) needs ratio > 1: sin_theta = sqrt(1 - cos^2) <= 1 (or NaN, which fails the
+  // compare) since cos^2 >= 0, so with ratio <= 1 — every front face, and both faces of an ir = 1 coat —
+  // the square root is skipped and the decision is the same
+  bool refl = ratio > 1.0 && ratio * sqrt_rn(1.0 - cos_theta * cos_theta) > 1.0;
+  if (!refl) {  // drawn only if not TIR: the uniform drawn ahead is consumed
+    PH_COUNT(22);
+    refl = reflectance_r0sq(cos_theta, h.front_face ? m.albedo[0] : m.albedo[1]) > r.x;
+    const uint64_t cb = double_as_u64(r.y);
+    rng.draw += 1u;
+    rng.c2 = (uint32_t)cb;
+    rng.c3 = (uint32_t)(cb >> 32);
+  }
+  o = h.point;
+  d = refl ? reflect(ud, h.normal) : refract(ud, h.normal, ratio);
+}
 // shade_pre<true> with the path's attenuation and emission left to the caller, so that the megakernel
 // reads and writes them once per segment instead of once per material branch: the material's
 // attenuation factor goes to `mul` (att = att * mul; 1 for a dielectric, exact) and its emission to
@@ -2402,7 +2496,9 @@ __device__ __forceinline__ bool shade_factor(const DScene& S, const DTex* texs, 
     has_emit = true;
     return false;
   }
-  if (m.kind == RT_MAT_DIELECTRIC) {  // dielectric.rs:21-49
+  // (shade_dielectric above is a copy of this branch: change both together — tests/test_gpu_hop.py's on/off
+  // frames differ when they drift)
+  if (m.kind == RT_MAT_DIELECTRIC) {  // dielectric.rs:21-49 (shade_dielectric is this branch on its own)
     PH_COUNT(17);
     double ratio = h.front_face ? m.inv_param : m.param;  // 1.0 / ir, precomputed
     const v3 ud = un;

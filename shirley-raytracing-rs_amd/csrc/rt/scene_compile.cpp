@@ -36,6 +36,7 @@ SceneTuning tuning_from_env() {
   t.no_lds_prims = getenv("SHIRLEY_NO_LDS_PRIMS") != nullptr;
   t.no_lds_mats = getenv("SHIRLEY_NO_LDS_MATS") != nullptr;
   t.no_lds_perlin = getenv("SHIRLEY_NO_LDS_PERLIN") != nullptr;
+  t.no_hop = getenv("SHIRLEY_NO_HOP") != nullptr;
   if (const char* e = getenv("SHIRLEY_SAH_BOXW")) t.sah_box_weight = atof(e);
   t.sah_binned = getenv("SHIRLEY_SAH_BINNED") != nullptr;
   t.wf_extend2 = getenv("SHIRLEY_WF_EXTEND2") != nullptr;
@@ -632,6 +633,14 @@ int plan_placement(const rt_scene_desc* d, int32_t placement, const SceneTuning&
   // n_lds_mats = 0).
   P.n_lds_mats = prims_lds ? n_mats : 0;
   P.n_lds_texs = prims_lds ? n_texs : 0;
+  // the hop pass (trace.hip): a reference scene in the scene-in-LDS instance that holds a RectBox with a
+  // dielectric material — the thin coat whose one-visit segments the pass serves (SHIRLEY_NO_HOP: never)
+  bool coat = false;
+  for (int i = 0; i < d->n_objects && !coat; ++i) {
+    const rt_object& o = d->objects[i];
+    coat = o.geometry == RT_GEOM_RECT_BOX && d->materials[o.material].kind == RT_MAT_DIELECTRIC;
+  }
+  P.hop_pass = coat && !ext && prims_lds && !tune.no_hop;  // tuning
 
   // wavefront extend block: its own (larger) stack area, the rest of LDS for nodes
   const long long wf_stack = (long long)wf_extend_lds(0, P.stack_depth);
@@ -654,6 +663,7 @@ int plan_placement(const rt_scene_desc* d, int32_t placement, const SceneTuning&
   cs.stats.n_nodes4 = n_nodes4;
   cs.stats.wide_block = P.wide ? 1 : 0;
   cs.stats.origin_limit = P.origin_limit;
+  cs.stats.hop_pass = P.hop_pass ? 1 : 0;
   cs.stats.device_bytes = (int64_t)(cs.nodes.size() * sizeof(DNode) + cs.prims.size() * sizeof(DPrim) +
                                     cs.mats.size() * sizeof(DMat) + cs.texs.size() * sizeof(DTex) +
                                     cs.perlin.size() * sizeof(DPerlin) + cs.texels.size());

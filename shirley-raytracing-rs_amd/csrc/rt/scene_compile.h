@@ -30,6 +30,7 @@ struct SceneTuning {
   bool no_lds_prims = false;    // SHIRLEY_NO_LDS_PRIMS
   bool no_lds_mats = false;     // SHIRLEY_NO_LDS_MATS
   bool no_lds_perlin = false;   // SHIRLEY_NO_LDS_PERLIN
+  bool no_hop = false;          // SHIRLEY_NO_HOP
   double sah_box_weight = 4.0;  // SHIRLEY_SAH_BOXW=<c>
   bool sah_binned = false;      // SHIRLEY_SAH_BINNED
   bool wf_extend2 = false;      // SHIRLEY_WF_EXTEND2
@@ -53,6 +54,7 @@ struct ScenePlacement {
   bool wf_extend4 = false;      // eligible for the 4-wide scene-in-LDS extend kernel (wf_prepare4 decides)
   int split_nt = 0;             // RT_ENGINE_SPLIT: traversal waves per block to try (0: scene not eligible)
   int split_refill = 0;         // SceneTuning.split_refill
+  bool hop_pass = false;        // the megakernel runs its instances with the hop pass (trace.hip)
 };
 
 // The plan's fields of the megakernel's device scene record.

@@ -59,7 +59,16 @@ constexpr int kNarrowWaves = RT_NARROW_WAVES;
 
 // LIST: the launch's tiles come from DWork.tile_list (an adaptive step, adaptive.h) — separate instances, so
 // that every other call runs the code it ran without the list.
-template <int THREADS, int MODE, bool EXT, bool LIST = false>
+// HOP: the hop pass at the end of the iteration body (below) — compiled only into the scene-in-LDS
+// reference-scene instances that launch_trace picks for a scene with a dielectric RectBox (ScenePlacement.hop_pass),
+// so every other instance keeps its code.
+#ifndef RT_HOP_MIN_LANES
+// the pass runs when at least this many lanes of the wave are candidates: 40 of {1, 8, 12, 16, 24, 32, 40, 48}
+// (the pass is ~3100 instructions of divergent leaf loops, so it pays only on waves looking at
+// the ground)
+#define RT_HOP_MIN_LANES 40
+#endif
+template <int THREADS, int MODE, bool EXT, bool LIST = false, bool HOP = false>
 __global__ __launch_bounds__(THREADS, THREADS >= kTraceThreadsWide3 ? 1 : (EXT ? RT_NARROW_WAVES_EXT : kNarrowWaves))
 void trace_kernel(KParams P) {
   extern __shared__ unsigned char lds_raw[];
@@ -384,6 +393,56 @@ void trace_kernel(KParams P) {
       active = true;
     }
     PH_STAMP(kPhTail);
+    // 5. the hop pass.  The reference scene's ground is a 0.01-thick dielectric RectBox coat over a Lambertian
+    // rect: each ground interaction adds segments whose closest hit is found at the tree's first node (the
+    // coat's far face from inside it, the coat from the rect), yet each holds its lane for a whole iteration
+    // whose length the other lanes' 5-9 node visits set.  A lane that goes on from a rect or RectBox hit tries
+    // its next segment here: when the first node decides the closest hit (traverse4_root) and that hit is a
+    // dielectric, the segment is done now — the same functions of (seed, pixel, sample, draw index, ray) in
+    // the same per-lane order as an iteration's steps 1, 3 and 4, so frames and counters are bit-identical
+    // with and without the pass.  Any other lane keeps its ray untouched and traverses from the root in the
+    // next iteration as before.  Wave-uniform: run only with enough candidates to pay for the wave's trip.
+    if constexpr (HOP) {
+      static_assert(MODE == kSceneLds && !EXT, "the hop pass is built for the scene-in-LDS reference-scene instances");
+      // (candidates by the hit's kind; measured and rejected, DESIGN.md §5: lanes that go on from a dielectric
+      // hit, −8 %, and RectBox hits from outside only, no better at any threshold)
+      bool cand = active && !regen && hit;
+      if (cand) cand = lds_prims[prim].kind != kPrimSphere;
+      if (__popcll(__ballot(cand)) >= RT_HOP_MIN_LANES) {
+        bool serve = false;
+        double t_hop = __builtin_inf();
+        int p_hop = -1, f_hop = -1;
+        if (cand) {
+          PH_COUNT(26);
+#ifdef RT_HOP_ROOT_OUTLINE
+          const RootHit rh = traverse4_root_ool<MODE>(lds_nodes, lds_prims, S.prims, S.root4, S.key_mask, S.origin_limit,
+                                                      o, d, rng, seed);
+          serve = rh.ok != 0;
+          t_hop = rh.t;
+          p_hop = rh.best;
+          f_hop = rh.face;
+#else
+          serve = traverse4_root<MODE>(S, lds_nodes, lds_prims, o, d, 0.001, t_hop, p_hop, f_hop, rng, seed, visits, ptests);
+#endif
+          if (serve) serve = mats[lds_prims[p_hop].material].kind == RT_MAT_DIELECTRIC;
+        }
+        n_seg += __popcll(__ballot(serve));
+        if (serve) {
+          PH_COUNT(27);
+          const DPrim pr = lds_prims[p_hop];
+          Hit hh;
+          hit_record<false, false>(S, pr, f_hop, o, d, t_hop, rng, seed, hh);
+          const v3 ru = draw_diel(rng, seed);
+          const v3 ud = unit_fast(d);
+          shade_dielectric(mats[pr.material], ru, ud, rng, o, d, hh);  // (att * 1 = att, no emission)
+          if (--depth_left <= 0) {
+            sum = sum + em;
+            active = false;  // takes its next sample in the next iteration's step 2
+          }
+        }
+      }
+      PH_STAMP(kPhTail);
+    }
 #ifdef RT_TIMELINE
     if (exhausted && !ph_exh_seen) {
       ph_exh_seen = true;
@@ -823,31 +882,32 @@ static int node_mode4(const DScene& S) {
   return S.n_lds_nodes4 >= S.n_nodes4 ? kNodesLds : (S.n_lds_nodes4 == 0 ? kNodesGlobal : kNodesMixed);
 }
 
-template <int THREADS, int MODE, bool EXT>
+template <int THREADS, int MODE, bool EXT, bool HOP = false>
 static hipError_t occupancy_impl1(const DScene& S, int* blocks_per_cu) {
   // allow dynamic LDS beyond the 64 KiB default (gfx950 has 160 KiB per CU)
   const size_t lds = trace_lds_bytes(S.n_lds_nodes4, node4_bytes(S.exts != nullptr), S.n_lds_prims, S.n_lds_perlin, S.stack_depth4, THREADS,
                                      S.n_lds_mats, S.n_lds_texs);
-  hipError_t e = hipFuncSetAttribute((const void*)trace_kernel<THREADS, MODE, EXT>,
+  hipError_t e = hipFuncSetAttribute((const void*)trace_kernel<THREADS, MODE, EXT, false, HOP>,
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e != hipSuccess) return e;
   // (the tile-list instance runs in the same launch shape: same block, same LDS)
-  e = hipFuncSetAttribute((const void*)trace_kernel<THREADS, MODE, EXT, true>,
+  e = hipFuncSetAttribute((const void*)trace_kernel<THREADS, MODE, EXT, true, HOP>,
                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e != hipSuccess) return e;
-  return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, trace_kernel<THREADS, MODE, EXT>, THREADS, lds);
+  return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, trace_kernel<THREADS, MODE, EXT, false, HOP>, THREADS,
+                                                      lds);
 }
 template <int THREADS, int MODE>
 static hipError_t occupancy_impl(const DScene& S, int* blocks_per_cu) {
   return S.exts ? occupancy_impl1<THREADS, MODE, true>(S, blocks_per_cu)
                 : occupancy_impl1<THREADS, MODE, false>(S, blocks_per_cu);
 }
-template <int THREADS, int MODE, bool EXT>
+template <int THREADS, int MODE, bool EXT, bool HOP = false>
 static void launch_trace2(const KParams& p, int blocks, size_t lds, hipStream_t stream) {
   if (p.work.tile_list)
-    hipLaunchKernelGGL((trace_kernel<THREADS, MODE, EXT, true>), dim3(blocks), dim3(THREADS), lds, stream, p);
+    hipLaunchKernelGGL((trace_kernel<THREADS, MODE, EXT, true, HOP>), dim3(blocks), dim3(THREADS), lds, stream, p);
   else
-    hipLaunchKernelGGL((trace_kernel<THREADS, MODE, EXT>), dim3(blocks), dim3(THREADS), lds, stream, p);
+    hipLaunchKernelGGL((trace_kernel<THREADS, MODE, EXT, false, HOP>), dim3(blocks), dim3(THREADS), lds, stream, p);
 }
 template <int THREADS, int MODE>
 static void launch_trace1(const KParams& p, int blocks, size_t lds, hipStream_t stream) {
@@ -867,12 +927,15 @@ static hipError_t hit_prepare(const DScene& S) {
 }
 
 // Kernel instances: the wide block only with the whole (4-wide) BVH in LDS.  Also prepares the
-// rt_scene_hit kernel for the scene.
-hipError_t trace_occupancy(const DScene& S, int threads, int* blocks_per_cu) {
+// rt_scene_hit kernel for the scene.  `hop` (ScenePlacement.hop_pass): the scene-in-LDS reference-scene instances
+// with the hop pass; an error for a scene that runs any other instance.
+hipError_t trace_occupancy(const DScene& S, int threads, bool hop, int* blocks_per_cu) {
   hipError_t e = hit_prepare(S);
   if (e != hipSuccess) return e;
+  if (hop && !(threads == kTraceThreadsWide && !S.exts && S.n_lds_prims > 0)) return hipErrorInvalidValue;
   if (threads == kTraceThreadsWide && !S.exts) {  // reference scenes only: book-2 scenes take kTraceThreadsWide3
     if (node_mode4(S) != kNodesLds) return hipErrorInvalidValue;
+    if (hop) return occupancy_impl1<kTraceThreadsWide, kSceneLds, false, true>(S, blocks_per_cu);
     if (S.n_lds_prims > 0) return occupancy_impl1<kTraceThreadsWide, kSceneLds, false>(S, blocks_per_cu);
     return occupancy_impl1<kTraceThreadsWide, kNodesLds, false>(S, blocks_per_cu);
   }
@@ -888,11 +951,14 @@ hipError_t trace_occupancy(const DScene& S, int threads, int* blocks_per_cu) {
   }
 }
 
-hipError_t launch_trace(const KParams& p, int blocks, int threads, hipStream_t stream) {
+hipError_t launch_trace(const KParams& p, int blocks, int threads, bool hop, hipStream_t stream) {
   const size_t lds = trace_lds_bytes(p.scene.n_lds_nodes4, node4_bytes(p.scene.exts != nullptr), p.scene.n_lds_prims, p.scene.n_lds_perlin, p.scene.stack_depth4, threads,
                                      p.scene.n_lds_mats, p.scene.n_lds_texs);
+  if (hop && !(threads == kTraceThreadsWide && !p.scene.exts && p.scene.n_lds_prims > 0)) return hipErrorInvalidValue;
   if (threads == kTraceThreadsWide && !p.scene.exts) {
-    if (p.scene.n_lds_prims > 0)
+    if (hop)
+      launch_trace2<kTraceThreadsWide, kSceneLds, false, true>(p, blocks, lds, stream);
+    else if (p.scene.n_lds_prims > 0)
       launch_trace2<kTraceThreadsWide, kSceneLds, false>(p, blocks, lds, stream);
     else
       launch_trace2<kTraceThreadsWide, kNodesLds, false>(p, blocks, lds, stream);
@@ -1088,8 +1154,8 @@ void phase_counters_dump() {
                                 "pop_iter", "segment_iter", "box_iter", "marble_round", "draws_coop_round",
                                 "unit_fetch", "camera_ray", "philox_A", "philox_B", "marble_sin", "hit_record",
                                 "checker_level", "dielectric", "metal", "lambertian", "sky", "diffuse_light",
-                                "reflectance", "traverse4", "publish", "tie_resolve"};
-  for (int i = 0; i < 26; ++i)
+                                "reflectance", "traverse4", "publish", "tie_resolve", "hop_candidate", "hop_served"};
+  for (int i = 0; i < 28; ++i)
     if (h[2 * i + 1])
       fprintf(stderr, "[phase-ev] %-18s lanes %.4g waves %.4g lanes/wave %.2f\n", names[i], (double)h[2 * i],
               (double)h[2 * i + 1], (double)h[2 * i] / (double)h[2 * i + 1]);

@@ -85,7 +85,9 @@ class rt_scene_stats(C.Structure):
     _fields_ = [("n_objects", C.c_int32), ("n_nodes", C.c_int32), ("n_leaves", C.c_int32),
                 ("depth", C.c_int32), ("device_bytes", C.c_int64),
                 # ABI 4
-                ("n_nodes4", C.c_int32), ("wide_block", C.c_int32), ("origin_limit", C.c_double)]
+                ("n_nodes4", C.c_int32), ("wide_block", C.c_int32), ("origin_limit", C.c_double),
+                # ABI 9
+                ("hop_pass", C.c_int32)]
 
 
 class rt_counters(C.Structure):
