@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define RT_ABI_VERSION 9
+#define RT_ABI_VERSION 10
 
 typedef enum rt_status {
   RT_OK = 0,
@@ -458,6 +458,89 @@ int rt_render_adaptive(rt_ctx* ctx, const rt_camera* cam, const rt_render_params
 int rt_tonemap_counts(const double* accum, const int32_t* counts, int32_t width, int32_t height, uint8_t* rgb8);
 int rt_tonemap_counts_device(rt_ctx* ctx, const double* accum_dev, const int32_t* counts_dev, int32_t width,
                              int32_t height, uint8_t* rgb8_dev, void* stream);
+
+/* ---- feature buffers and the à-trous denoiser (ABI 10) ----------------------------
+ * Feature buffers: per-pixel SUMS over the call's sample range of the albedo, the normal and the depth seen
+ * along each sample's own path — the auxiliary images a reconstruction filter is guided by.  Sample s of
+ * pixel p runs on the render's path key (seed, p, s): the render's camera ray (jitter draws 0 and 1, then
+ * the lens-disk draws), then the render's own dielectric segments.
+ *   depth   the camera ray's closest-hit t in [0.001, inf); 0 on a miss.
+ *   chain   the path is followed while its closest hit is RT_MAT_DIELECTRIC and fewer than `chain` dielectric
+ *           vertices have been followed (chain >= 0; 0 = the first hit).  Each step is exactly the renderer's
+ *           dielectric segment — the same draw index, odd-half cache and Schlick decision — i.e. what
+ *           rt_probe_segment returns when called with the path's running draw counter.
+ *   feature vertex (where the chain stops)
+ *           miss: albedo = the sky colour of that ray (rt_probe.emitted), normal = 0;
+ *           hit:  normal = the hit record's normal; albedo = rt_material.albedo (Metal), (1, 1, 1)
+ *           (Dielectric: chain exhausted), else the material's texture value at the record's (u, v, point)
+ *           (Lambertian, DiffuseLight, FairyLight: no direction factor, no normalisation).
+ * params->samples, seed, sample_begin and sample_count mean what they mean for rt_render; tile_world must be
+ * 1; max_depth, engine, sample_chunk and scratch_mb are ignored.  Samples are added in order.
+ * albedo / normal: [H][W][3] f64, depth: [H][W] f64, row 0 = bottom; any of the three may be NULL.
+ * Scenes with book-2 objects return RT_E_UNSUPPORTED (a ray's first hit in a medium is a random variable).
+ * rt_render_features blocks; rt_render_features_device takes device pointers and is asynchronous on `stream`
+ * (NULL: the context's stream), like rt_render_device. */
+int rt_render_features(rt_ctx* ctx, const rt_camera* cam, const rt_render_params* params, int32_t chain,
+                       double* albedo_host, double* normal_host, double* depth_host);
+int rt_render_features_device(rt_ctx* ctx, const rt_camera* cam, const rt_render_params* params, int32_t chain,
+                              double* albedo_dev, double* normal_dev, double* depth_dev, void* stream);
+
+/* The filter: an edge-aware à-trous wavelet filter (Dammertz et al. 2010) on the albedo-demodulated frame.
+ * With c, a, n, z the per-pixel means (sums / their sample counts) and A = max(a, albedo_floor) per channel:
+ *   prepare    c^ = c / A per channel;  var^ = variance / ((A_r^2 + A_g^2 + A_b^2) / 3)
+ *   iterations i = 0 .. iterations-1 with stride s = 2^i over the 5x5 taps h = (1/16, 1/4, 3/8, 1/4, 1/16) x h
+ *              at offsets s (dx, dy), dy = -2..2 outer, dx = -2..2 inner, taps outside the image skipped:
+ *                c^'_p = sum_q h_q w_pq c^_q / sum_q h_q w_pq
+ *                var^'_p = sum_q (h_q w_pq)^2 var^_q / (sum_q h_q w_pq)^2
+ *              w_pp = 1;  w_pq = ((w_n w_z) w_a) w_c for q != p, with f(x) = max(0, 1 - x)^2:
+ *                w_n  1 when |n_p|^2 = |n_q|^2 = 0 (both sky), 0 when exactly one is 0, else
+ *                     max(0, n_p.n_q)^2 / (|n_p|^2 |n_q|^2) squared normal_power_log2 times (4: cos^32)
+ *                w_z  f(r^2), r = (z_p - z_q) / (sigma_z (z_p + z_q) + 1e-300)
+ *                w_a  f(|a_p - a_q|^2 / sigma_a^2)
+ *                w_c  f(|c^_p - c^_q|^2 / (sigma_c^2 (var^_p + var^_q) + 1e-300)) on the iteration's input
+ *                     values; 1 when `variance` is NULL
+ *   finish     out = (c^ A) count
+ * Only + - * /, comparisons and selects in a fixed order (no libm, no fused multiply-add): the device result
+ * equals the host's bit for bit.  A pixel whose c^ is not finite is copied through unchanged and has weight 0
+ * as a neighbour; a pixel with count 0 outputs 0 and is not used as a neighbour.  iterations == 0 returns
+ * the input sums.  Defaults (the Python binding's and ray-cli's): iterations 3, normal_power_log2 4,
+ * sigma_z 0.05, sigma_a 0.2, sigma_c 2, albedo_floor 1e-3.  RT_E_INVALID: iterations outside [0, 8],
+ * normal_power_log2 outside [0, 16], a sigma or the floor not > 0, a negative count, samples < 1 without
+ * counts, feature_samples < 1, a NULL accum / albedo / normal / depth. */
+typedef struct rt_denoise_inputs {
+  int32_t width, height;
+  int32_t samples;          /* every pixel's sample count when counts == NULL */
+  int32_t feature_samples;  /* samples summed in albedo / normal / depth */
+  const double* accum;      /* [H][W][3] sums (rt_render / rt_render_adaptive), row order as theirs */
+  const int32_t* counts;    /* [H][W] per-pixel sample counts (an adaptive frame), or NULL */
+  const double* albedo;     /* [H][W][3] sums (rt_render_features) */
+  const double* normal;     /* [H][W][3] sums */
+  const double* depth;      /* [H][W] sums */
+  const double* variance;   /* [H][W] variance of the pixel's MEAN r + g + b, or NULL: no colour term */
+} rt_denoise_inputs;
+
+typedef struct rt_denoise_params {
+  int32_t iterations;         /* [0, 8]; stride 2^i in iteration i */
+  int32_t normal_power_log2;  /* [0, 16] */
+  double sigma_z, sigma_a, sigma_c;
+  double albedo_floor;
+} rt_denoise_params;
+
+/* out_sums: [H][W][3] on the input's scale (filtered mean x the pixel's count): rt_tonemap / rt_tonemap_counts
+ * apply unchanged.  rt_denoise runs on the host and needs no device; rt_denoise_device takes device pointers
+ * in `in` and out_sums_dev, is asynchronous on `stream` (NULL: the context's stream) and uses scratch of its
+ * own kept on the context (a negative count is not diagnosed there: such a pixel is treated as count 0). */
+int rt_denoise(const rt_denoise_inputs* in, const rt_denoise_params* params, double* out_sums);
+int rt_denoise_device(rt_ctx* ctx, const rt_denoise_inputs* in, const rt_denoise_params* params,
+                      double* out_sums_dev, void* stream);
+
+/* rt_render_adaptive's moments ([H][W][2] m1, m2 over batches of `batch` samples) and counts ([H][W]) to the
+ * filter's variance input: out[p] = v_p n / N^2 with n = counts[p] / batch batches, N = counts[p] samples and
+ * v_p the batch-means variance above (NaN for n < 2).  Host and device (asynchronous on `stream`) forms. */
+int rt_moments_variance(const double* moments, const int32_t* counts, int32_t batch, int32_t width, int32_t height,
+                        double* out);
+int rt_moments_variance_device(rt_ctx* ctx, const double* moments_dev, const int32_t* counts_dev, int32_t batch,
+                               int32_t width, int32_t height, double* out_dev, void* stream);
 
 #ifdef __cplusplus
 }

@@ -46,6 +46,8 @@ struct Args {
   bool adaptive = false;
   double adaptive_threshold = 0.0, noise_floor = 0.01;
   int min_samples = 16, adaptive_step = 16;
+  int denoise = -1, denoise_chain = 8;  // --denoise [N]: à-trous iterations (-1: off)
+  bool denoise_variance = false;
   double fov = 20.0, focal = 1.0, aperture = 0.001;
   bool night = false, single_threaded = false;
   unsigned long long seed = 0x5EED;
@@ -61,7 +63,8 @@ struct Args {
                "         --night --scene-output FILE (random)  <scene_input> (saved)  --side-len N (spheres)\n"
                "         --seed N --device N --gpus N --partition tiles|samples --bvh reference|sah --sample-chunk N\n"
                "         --dump-accum FILE --progressive K --resume FILE\n"
-               "         --adaptive T --min-samples N --adaptive-step N --noise-floor F\n");
+               "         --adaptive T --min-samples N --adaptive-step N --noise-floor F\n"
+               "         --denoise [N] --denoise-chain K --denoise-variance (with --adaptive)\n");
   std::exit(2);
 }
 
@@ -206,6 +209,81 @@ int render_scene_multi(const Args& a, const rt_scene_desc* desc, const rt_camera
   return done(0);
 }
 
+// --denoise: the à-trous filter (rt_denoise_device) between the frame's sums and the tonemap.  The feature
+// buffers are rendered over `feature_samples` samples of the frame ([0, feature_samples)); counts (an adaptive
+// frame) and variance may be null.  Fills rgb; false on an error (already printed).
+struct DevMem {
+  std::vector<void*> p;
+  ~DevMem() {
+    for (void* q : p) (void)hipFree(q);
+  }
+  template <class T>
+  T* get(size_t n, const T* host = nullptr) {
+    void* q = nullptr;
+    if (hipMalloc(&q, n * sizeof(T)) != hipSuccess) return nullptr;
+    p.push_back(q);
+    if (host && hipMemcpy(q, host, n * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) return nullptr;
+    return static_cast<T*>(q);
+  }
+};
+
+bool denoise_to_rgb(const Args& a, rt_ctx* ctx, const rt_camera& cam, const rt_render_params& frame, int samples,
+                    int feature_samples, const double* accum, const int32_t* counts, const double* variance,
+                    std::vector<uint8_t>& rgb) {
+  const int W = cam.image_width, H = cam.image_height;
+  const size_t n_px = (size_t)W * H;
+  DevMem mem;
+  double* acc_dev = mem.get<double>(n_px * 3, accum);
+  double* alb_dev = mem.get<double>(n_px * 3);
+  double* nrm_dev = mem.get<double>(n_px * 3);
+  double* dep_dev = mem.get<double>(n_px);
+  double* out_dev = mem.get<double>(n_px * 3);
+  uint8_t* rgb_dev = mem.get<uint8_t>(n_px * 3);
+  int32_t* cnt_dev = counts ? mem.get<int32_t>(n_px, counts) : nullptr;
+  double* var_dev = variance ? mem.get<double>(n_px, variance) : nullptr;
+  if (!acc_dev || !alb_dev || !nrm_dev || !dep_dev || !out_dev || !rgb_dev || (counts && !cnt_dev) ||
+      (variance && !var_dev)) {
+    std::fprintf(stderr, "error: device allocation of the denoiser's images failed\n");
+    return false;
+  }
+  rt_render_params fp = frame;
+  fp.sample_begin = 0;
+  fp.sample_count = feature_samples;
+  rt_denoise_inputs in{};
+  in.width = W;
+  in.height = H;
+  in.samples = samples;
+  in.feature_samples = feature_samples;
+  in.accum = acc_dev;
+  in.counts = cnt_dev;
+  in.albedo = alb_dev;
+  in.normal = nrm_dev;
+  in.depth = dep_dev;
+  in.variance = var_dev;
+  rt_denoise_params dp{};  // the documented defaults (include/shirley_rt.h)
+  dp.iterations = a.denoise;
+  dp.normal_power_log2 = 4;
+  dp.sigma_z = 0.05;
+  dp.sigma_a = 0.2;
+  dp.sigma_c = 2.0;
+  dp.albedo_floor = 1e-3;
+  int st = rt_render_features_device(ctx, &cam, &fp, a.denoise_chain, alb_dev, nrm_dev, dep_dev, nullptr);
+  if (!st) st = rt_denoise_device(ctx, &in, &dp, out_dev, nullptr);
+  if (!st)
+    st = counts ? rt_tonemap_counts_device(ctx, out_dev, cnt_dev, W, H, rgb_dev, nullptr)
+                : rt_tonemap_device(ctx, out_dev, W, H, samples, rgb_dev, nullptr);
+  if (!st) st = rt_synchronize(ctx);
+  if (st) {
+    std::fprintf(stderr, "error: --denoise: %s\n", rt_last_error(ctx));
+    return false;
+  }
+  if (hipMemcpy(rgb.data(), rgb_dev, n_px * 3, hipMemcpyDeviceToHost) != hipSuccess) {
+    std::fprintf(stderr, "error: --denoise: copying the picture back failed\n");
+    return false;
+  }
+  return true;
+}
+
 int render_scene(const Args& a, const rt_scene_desc* desc, const rt_camera& cam) {
   int samples = a.samples;
   if (samples == 0) {  // main.rs:75-80
@@ -213,6 +291,15 @@ int render_scene(const Args& a, const rt_scene_desc* desc, const rt_camera& cam)
     samples = 1;
   }
   if (a.gpus > 1) return render_scene_multi(a, desc, cam, samples);
+  if (a.denoise >= 0)
+    for (int i = 0; i < desc->n_objects; ++i) {
+      const rt_object& o = desc->objects[i];
+      if (o.geometry == RT_GEOM_MOVING_SPHERE || o.medium || o.transform) {
+        std::fprintf(stderr, "error: --denoise: the feature pass does not support book-2 objects (moving spheres, "
+                             "media, instance transforms); object %d is one\n", i);
+        return 1;
+      }
+    }
   rt_ctx* ctx = nullptr;
   int st = rt_create(a.device, &ctx);
   if (st) {
@@ -247,12 +334,26 @@ int render_scene(const Args& a, const rt_scene_desc* desc, const rt_camera& cam)
     accum.resize(n);
     std::vector<int32_t> counts(n / 3);
     rt_adaptive_report rep{};
-    if ((st = rt_render_adaptive(ctx, &cam, &p, &ap, accum.data(), counts.data(), nullptr, nullptr, &rep))) {
+    std::vector<double> moments(a.denoise_variance ? n / 3 * 2 : 0), variance(a.denoise_variance ? n / 3 : 0);
+    if ((st = rt_render_adaptive(ctx, &cam, &p, &ap, accum.data(), counts.data(),
+                                 a.denoise_variance ? moments.data() : nullptr, nullptr, &rep))) {
       std::fprintf(stderr, "error: %s\n", rt_last_error(ctx));
       rt_destroy(ctx);
       return 1;
     }
-    rt_tonemap_counts(accum.data(), counts.data(), cam.image_width, cam.image_height, rgb.data());
+    if (a.denoise >= 0) {
+      // the features come from the samples every pixel holds, [0, min_samples); the counts from the call
+      if (a.denoise_variance)
+        rt_moments_variance(moments.data(), counts.data(), a.sample_chunk ? a.sample_chunk : 4, cam.image_width,
+                            cam.image_height, variance.data());
+      if (!denoise_to_rgb(a, ctx, cam, p, samples, a.min_samples, accum.data(), counts.data(),
+                          a.denoise_variance ? variance.data() : nullptr, rgb)) {
+        rt_destroy(ctx);
+        return 1;
+      }
+    } else {
+      rt_tonemap_counts(accum.data(), counts.data(), cam.image_width, cam.image_height, rgb.data());
+    }
     if (verbose >= 1)
       std::fprintf(stderr, "INFO adaptive: %d steps, mean %.2f spp of at most %d, %.1f %% of %d tiles converged\n",
                    rep.steps, (double)rep.samples / (double)(n / 3), samples,
@@ -318,14 +419,21 @@ int render_scene(const Args& a, const rt_scene_desc* desc, const rt_camera& cam)
       }
     }
     return 0;
-  } else if (!a.dump_accum.empty()) {  // the raw sums are wanted on the host: render + host tonemap
+  } else if (!a.dump_accum.empty() || a.denoise >= 0) {  // the raw sums are wanted on the host: render + host tonemap
     accum.resize(n);
     if ((st = rt_render(ctx, &cam, &p, accum.data()))) {
       std::fprintf(stderr, "error: %s\n", rt_last_error(ctx));
       rt_destroy(ctx);
       return 1;
     }
-    rt_tonemap(accum.data(), cam.image_width, cam.image_height, samples, rgb.data());  // image.rs:31-44
+    if (a.denoise >= 0) {  // features over the frame's samples, filter, tonemap: all on the device
+      if (!denoise_to_rgb(a, ctx, cam, p, samples, samples, accum.data(), nullptr, nullptr, rgb)) {
+        rt_destroy(ctx);
+        return 1;
+      }
+    } else {
+      rt_tonemap(accum.data(), cam.image_width, cam.image_height, samples, rgb.data());  // image.rs:31-44
+    }
   } else {  // sums stay in HBM; to_image runs on the device and only RGB8 crosses PCIe
     double* acc_dev = nullptr;
     uint8_t* rgb_dev = nullptr;
@@ -401,6 +509,12 @@ int main(int argc, char** argv) {
     else if (s == "--min-samples") a.min_samples = std::atoi(next().c_str());
     else if (s == "--adaptive-step") a.adaptive_step = std::atoi(next().c_str());
     else if (s == "--noise-floor") a.noise_floor = std::atof(next().c_str());
+    else if (s == "--denoise") {  // the iteration count is optional: taken when the next argument is a number
+      a.denoise = 3;
+      if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') a.denoise = std::atoi(argv[++i]);
+    }
+    else if (s == "--denoise-chain") a.denoise_chain = std::atoi(next().c_str());
+    else if (s == "--denoise-variance") a.denoise_variance = true;
     else if (s == "--partition") {
       const std::string v = next();
       if (v == "tiles") a.partition = RT_PARTITION_TILES;
@@ -428,6 +542,12 @@ int main(int argc, char** argv) {
   if (a.adaptive && (a.gpus > 1 || a.progressive > 1 || !a.resume.empty()))
     usage("--adaptive renders on one GPU, without --progressive / --resume");
   if (a.adaptive && !a.dump_accum.empty()) usage("--adaptive frames are not checkpointed (--dump-accum)");
+
+  if (a.denoise >= 0 && (a.gpus > 1 || a.progressive > 1 || !a.resume.empty()))
+    usage("--denoise filters a frame rendered on one GPU, without --progressive / --resume");
+  if (a.denoise > 8 || a.denoise_chain < 0) usage("--denoise takes 0 to 8 iterations, --denoise-chain K >= 0");
+  if (a.denoise_variance && !(a.adaptive && a.denoise >= 0))
+    usage("--denoise-variance feeds the moments of an --adaptive frame to --denoise");
 
   sh_scene* scene = nullptr;
   std::string cam_scene = a.scene;

@@ -46,7 +46,6 @@ int upload(rt_ctx* c, DevBuf& b, const void* src, size_t bytes) {
   return RT_OK;
 }
 
-namespace {
 DCamera device_camera(const rt_camera* c) {
   // camera/mod.rs:99-108, evaluated once with the reference's operation order (-ffp-contract=off)
   DCamera d{};
@@ -70,8 +69,6 @@ DCamera device_camera(const rt_camera* c) {
                       c->w[k] * (c->focal_length * c->focus_length);
   return d;
 }
-
-}  // namespace
 
 int check_render_args(rt_ctx* c, const rt_camera* cam, const rt_render_params* p) {
   if (!c) return RT_E_INVALID;
@@ -506,7 +503,7 @@ int rt_destroy(rt_ctx* c) {
   if (!c) return RT_OK;
   (void)hipSetDevice(c->device);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
-  for (DevBuf* b : {&c->nodes, &c->nodes4, &c->prims, &c->mats, &c->texs, &c->perlin, &c->texels, &c->exts, &c->partial, &c->kcam, &c->shutter0, &c->moments, &c->tile_list, &c->tile_err,
+  for (DevBuf* b : {&c->nodes, &c->nodes4, &c->prims, &c->mats, &c->texs, &c->perlin, &c->texels, &c->exts, &c->partial, &c->kcam, &c->shutter0, &c->moments, &c->tile_list, &c->tile_err, &c->dn_a, &c->dn_b, &c->feat,
                     &c->accum, &c->counters, &c->unit_counter, &c->wf_pool, &c->wf_iters, &c->packed, &c->gathered,
                     &c->parts, &c->band, &c->digests})
     release(*b);

@@ -60,6 +60,8 @@ struct rt_ctx {
   // per-render scratch
   DevBuf partial, accum, counters, unit_counter, kcam;
   DevBuf moments, tile_list, tile_err;  // rt_render_adaptive: [H][W][2] moments, a step's tile list and its errors
+  DevBuf dn_a, dn_b;  // rt_denoise_device: the two [H][W][12] record buffers an iteration reads / writes
+  DevBuf feat;        // rt_render_features: the device buffers behind the host copies
   DevBuf shutter0;  // {0, 0}: the shutter of rt_scene_hit / rt_probe_segment queries (DScene.shutter)
   DevBuf wf_pool, wf_iters;          // path slots (SoA) + texture queue; per-iteration counters ring
   uint32_t* wf_host = nullptr;       // pinned readback of the retired-slot count, one word per batch
@@ -106,6 +108,7 @@ inline int fail(rt_ctx* c, int code, const char* fmt, ...) {
   } while (0)
 
 // rt_api.cpp
+DCamera device_camera(const rt_camera* c);
 int ensure(rt_ctx* c, DevBuf& b, size_t bytes);
 void release(DevBuf& b);
 int upload(rt_ctx* c, DevBuf& b, const void* src, size_t bytes);

@@ -1,7 +1,8 @@
 // rt_launch.h — the launch wrappers of the HIP files, as the host side of the C ABI calls them.
 //
-// Included by rt_api.cpp / rt_multi.cpp and by the files that define the wrappers (trace.hip,
-// trace_split.hip, wavefront.hip), so a changed signature fails to compile where it is changed.
+// Included by rt_api.cpp, rt_multi.cpp, rt_denoise.cpp and by the files that define the wrappers (trace.hip,
+// trace_split.hip, wavefront.hip, features.hip, denoise.hip), so a changed signature fails to compile where
+// it is changed.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -36,6 +37,14 @@ hipError_t launch_hit4(const DScene& S, bool wide, const double* rays, int n, do
                        hipStream_t stream);
 hipError_t launch_probe(const DScene& S, bool wide, const double* rays, int n, uint64_t seed, uint32_t sample,
                         uint32_t draw, void* out, hipStream_t stream);
+// features.hip
+hipError_t launch_features(const DScene& S, bool wide, const DCamera& C, uint64_t seed, int s_begin, int s_end,
+                           int chain, double* albedo, double* normal, double* depth, hipStream_t stream);
+// denoise.hip
+hipError_t launch_denoise(const rt_denoise_inputs& in, const rt_denoise_params& prm, double* recs_a, double* recs_b,
+                          double* out, hipStream_t stream);
+hipError_t launch_moments_variance(const double* moments, const int32_t* counts, int batch, long long n, double* out,
+                                   hipStream_t stream);
 // trace_split.hip
 bool split_supported_nt(int nt);
 hipError_t split_prepare(const DScene& S, int nt, int* blocks_per_cu);

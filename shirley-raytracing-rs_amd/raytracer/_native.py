@@ -112,6 +112,17 @@ class rt_adaptive_report(C.Structure):  # ABI 8
                 ("fold_ms", C.c_double)]
 
 
+class rt_denoise_inputs(C.Structure):  # ABI 10
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("samples", C.c_int32), ("feature_samples", C.c_int32),
+                ("accum", C.c_void_p), ("counts", C.c_void_p), ("albedo", C.c_void_p), ("normal", C.c_void_p),
+                ("depth", C.c_void_p), ("variance", C.c_void_p)]
+
+
+class rt_denoise_params(C.Structure):  # ABI 10
+    _fields_ = [("iterations", C.c_int32), ("normal_power_log2", C.c_int32), ("sigma_z", C.c_double),
+                ("sigma_a", C.c_double), ("sigma_c", C.c_double), ("albedo_floor", C.c_double)]
+
+
 class rt_bvh_node(C.Structure):
     _fields_ = [("box", _d6), ("leaf", C.c_int32), ("lhs", C.c_int32), ("rhs", C.c_int32), ("pad", C.c_int32)]
 
@@ -181,6 +192,17 @@ RT_SIGNATURES = {
     "rt_tonemap_counts": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
     "rt_tonemap_counts_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
                                            C.c_void_p]),
+    # ABI 10
+    "rt_render_features": (C.c_int, [C.c_void_p, C.POINTER(rt_camera), C.POINTER(rt_render_params), C.c_int32,
+                                     C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_render_features_device": (C.c_int, [C.c_void_p, C.POINTER(rt_camera), C.POINTER(rt_render_params), C.c_int32,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_denoise": (C.c_int, [C.POINTER(rt_denoise_inputs), C.POINTER(rt_denoise_params), C.c_void_p]),
+    "rt_denoise_device": (C.c_int, [C.c_void_p, C.POINTER(rt_denoise_inputs), C.POINTER(rt_denoise_params),
+                                    C.c_void_p, C.c_void_p]),
+    "rt_moments_variance": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "rt_moments_variance_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                             C.c_void_p, C.c_void_p]),
 }
 
 # every symbol declared in include/shirley_host.h

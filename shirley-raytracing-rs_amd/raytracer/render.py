@@ -68,6 +68,69 @@ class AdaptiveSettings:
         return a
 
 
+@dataclass
+class DenoiseSettings:
+    """rt_denoise_params with the documented defaults (include/shirley_rt.h)."""
+    iterations: int = 3
+    normal_power_log2: int = 4
+    sigma_z: float = 0.05
+    sigma_a: float = 0.2
+    sigma_c: float = 2.0
+    albedo_floor: float = 1e-3
+
+    def params(self) -> N.rt_denoise_params:
+        p = N.rt_denoise_params()
+        p.iterations, p.normal_power_log2 = int(self.iterations), int(self.normal_power_log2)
+        p.sigma_z, p.sigma_a, p.sigma_c = float(self.sigma_z), float(self.sigma_a), float(self.sigma_c)
+        p.albedo_floor = float(self.albedo_floor)
+        return p
+
+
+def _denoise_inputs(width, height, accum_ptr, albedo_ptr, normal_ptr, depth_ptr, samples, feature_samples,
+                    counts_ptr=0, variance_ptr=0) -> N.rt_denoise_inputs:
+    i = N.rt_denoise_inputs()
+    i.width, i.height, i.samples, i.feature_samples = int(width), int(height), int(samples), int(feature_samples)
+    i.accum, i.albedo, i.normal, i.depth = accum_ptr or None, albedo_ptr or None, normal_ptr or None, depth_ptr or None
+    i.counts, i.variance = counts_ptr or None, variance_ptr or None
+    return i
+
+
+def denoise(accum: np.ndarray, albedo: np.ndarray, normal: np.ndarray, depth: np.ndarray, samples: int = 0,
+            feature_samples: int = 0, settings: Optional[DenoiseSettings] = None,
+            counts: Optional[np.ndarray] = None, variance: Optional[np.ndarray] = None) -> np.ndarray:
+    """rt_denoise on the host (no device): the à-trous filter on [H][W][3] sums `accum`, guided by the feature
+    sums (Device.render_features over `feature_samples` samples, default: `samples`) -> filtered [H][W][3]
+    sums on accum's scale.  `counts` [H][W] replaces the scalar `samples` for an adaptive frame; `variance`
+    [H][W] (the variance of each pixel's mean r+g+b, moments_variance) turns the colour term on."""
+    h, w, _ = accum.shape
+    f64 = lambda a, shape: np.ascontiguousarray(a, dtype=np.float64).reshape(shape)  # noqa: E731
+    a, al, no, de = f64(accum, (h, w, 3)), f64(albedo, (h, w, 3)), f64(normal, (h, w, 3)), f64(depth, (h, w))
+    cn = None if counts is None else np.ascontiguousarray(counts, dtype=np.int32).reshape(h, w)
+    va = None if variance is None else f64(variance, (h, w))
+    out = np.zeros((h, w, 3), dtype=np.float64)
+    i = _denoise_inputs(w, h, a.ctypes.data, al.ctypes.data, no.ctypes.data, de.ctypes.data, samples,
+                        feature_samples or samples, 0 if cn is None else cn.ctypes.data,
+                        0 if va is None else va.ctypes.data)
+    p = (settings or DenoiseSettings()).params()
+    code = N.rt_lib().rt_denoise(C.byref(i), C.byref(p), out.ctypes.data)
+    if code:
+        raise N.RtError(code, "rt_denoise: invalid argument")
+    return out
+
+
+def moments_variance(moments: np.ndarray, counts: np.ndarray, batch: int) -> np.ndarray:
+    """rt_moments_variance: render_adaptive's moments and counts -> [H][W] variance of each pixel's mean r+g+b
+    (`batch`: the frame's sample_chunk, 0 = 4)."""
+    h, w = counts.shape
+    m = np.ascontiguousarray(moments, dtype=np.float64).reshape(h, w, 2)
+    n = np.ascontiguousarray(counts, dtype=np.int32)
+    out = np.zeros((h, w), dtype=np.float64)
+    code = N.rt_lib().rt_moments_variance(m.ctypes.data, n.ctypes.data, int(batch) or 4, w, h, out.ctypes.data)
+    if code:
+        raise N.RtError(code, "rt_moments_variance: invalid argument")
+    return out
+
+
 class Device:
     """One rt_ctx (one MI355X)."""
 
@@ -132,6 +195,44 @@ class Device:
                                                       accum.ctypes.data, counts.ctypes.data, moments.ctypes.data,
                                                       tile_error.ctypes.data, C.byref(report)))
         return accum, counts, moments, tile_error, report
+
+    def render_features(self, camera: N.rt_camera, settings: RenderSettings, chain: int = 8):
+        """rt_render_features -> (albedo [H][W][3], normal [H][W][3], depth [H][W]) f64 sums over the settings'
+        sample range, row 0 = bottom; `chain`: dielectric vertices a sample's path is followed through."""
+        h, w = camera.image_height, camera.image_width
+        albedo = np.zeros((h, w, 3), dtype=np.float64)
+        normal = np.zeros((h, w, 3), dtype=np.float64)
+        depth = np.zeros((h, w), dtype=np.float64)
+        p = settings.params()
+        _check(self._h, N.rt_lib().rt_render_features(self._h, C.byref(camera), C.byref(p), int(chain),
+                                                      albedo.ctypes.data, normal.ctypes.data, depth.ctypes.data))
+        return albedo, normal, depth
+
+    def render_features_device(self, camera, settings: RenderSettings, chain: int, albedo_ptr: int, normal_ptr: int,
+                               depth_ptr: int, stream: int = 0):
+        """rt_render_features_device: device [H][W][3], [H][W][3], [H][W] f64 outputs (a pointer may be 0)."""
+        p = settings.params()
+        _check(self._h, N.rt_lib().rt_render_features_device(
+            self._h, C.byref(camera), C.byref(p), int(chain), C.c_void_p(albedo_ptr or None),
+            C.c_void_p(normal_ptr or None), C.c_void_p(depth_ptr or None), C.c_void_p(stream or None)))
+
+    def denoise_device(self, width: int, height: int, accum_ptr: int, albedo_ptr: int, normal_ptr: int,
+                       depth_ptr: int, out_ptr: int, samples: int = 0, feature_samples: int = 0,
+                       settings: Optional[DenoiseSettings] = None, counts_ptr: int = 0, variance_ptr: int = 0,
+                       stream: int = 0):
+        """rt_denoise_device: `denoise` on device buffers, asynchronous on `stream`; bit-identical to the host's."""
+        i = _denoise_inputs(width, height, accum_ptr, albedo_ptr, normal_ptr, depth_ptr, samples,
+                            feature_samples or samples, counts_ptr, variance_ptr)
+        p = (settings or DenoiseSettings()).params()
+        _check(self._h, N.rt_lib().rt_denoise_device(self._h, C.byref(i), C.byref(p), C.c_void_p(out_ptr or None),
+                                                     C.c_void_p(stream or None)))
+
+    def moments_variance_device(self, moments_ptr: int, counts_ptr: int, batch: int, width: int, height: int,
+                                out_ptr: int, stream: int = 0):
+        """rt_moments_variance_device: `moments_variance` on device buffers."""
+        _check(self._h, N.rt_lib().rt_moments_variance_device(
+            self._h, C.c_void_p(moments_ptr or None), C.c_void_p(counts_ptr or None), int(batch) or 4, int(width),
+            int(height), C.c_void_p(out_ptr or None), C.c_void_p(stream or None)))
 
     def tonemap_counts_device(self, accum_ptr: int, counts_ptr: int, width: int, height: int, rgb8_ptr: int,
                               stream: int = 0):
