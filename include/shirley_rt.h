@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define RT_ABI_VERSION 10
+#define RT_ABI_VERSION 11
 
 typedef enum rt_status {
   RT_OK = 0,
@@ -541,6 +541,40 @@ int rt_moments_variance(const double* moments, const int32_t* counts, int32_t ba
                         double* out);
 int rt_moments_variance_device(rt_ctx* ctx, const double* moments_dev, const int32_t* counts_dev, int32_t batch,
                                int32_t width, int32_t height, double* out_dev, void* stream);
+
+/* ---- occlusion queries and the ambient-occlusion pass (ABI 11) ---------------------
+ * Any-hit query: out[i] = 1 iff some object is hit by ray i with t in [t_min, tmax_i], tmax_i = t_max_each ?
+ * t_max_each[i] : t_max — exactly when rt_scene_hit_ex(RT_TRAVERSAL_RENDER) on [t_min, tmax_i] reports
+ * object >= 0; else 0.  The walk is the render traversal's with its accept decisions unchanged, but it never
+ * shrinks t_max and ends on the first accepted object.  A per-ray bound is what a shadow ray needs: the
+ * distance to the light.  Rays are finite with non-zero directions.  n == 0 is RT_OK.  RT_E_INVALID: a NULL
+ * rays or out, n < 0, a NaN t_min or t_max, no scene uploaded.  Scenes with book-2 objects return
+ * RT_E_UNSUPPORTED (a medium's hit is a random variable, a moving sphere needs a ray time).
+ * rt_scene_occluded blocks; rt_scene_occluded_device takes device pointers and is asynchronous on `stream`
+ * (NULL: the context's stream), like rt_render_features_device. */
+int rt_scene_occluded(rt_ctx* ctx, const double* rays /* [n][6] */, int32_t n, double t_min, double t_max,
+                      const double* t_max_each /* [n] or NULL */, uint8_t* out /* [n] */);
+int rt_scene_occluded_device(rt_ctx* ctx, const double* rays_dev, int32_t n, double t_min, double t_max,
+                             const double* t_max_each_dev, uint8_t* out_dev, void* stream);
+
+/* Ambient occlusion: per-pixel SUMS over the call's sample range of a 0/1 visibility ([H][W] f64, row 0 =
+ * bottom).  Sample s of pixel p runs on the render's path key (seed, p, s): rt_render_features's camera ray
+ * and dielectric chain (the same `chain` >= 0) to the feature vertex, where the path's draw counter is D.
+ *   miss       visibility 1.
+ *   direction  the renderer's Lambertian scatter at that record, whatever the material: r =
+ *              random_in_unit_sphere on draws D, D+1, ...; w = normal + unit(r), or normal where w is near
+ *              zero (lambertian.rs:21-37) — at a Lambertian vertex the render's own next ray, bit for bit.
+ *   occlusion  t_max = radius / |w| (radius = +inf: +inf); visibility 0 iff the ray (point, w) is occluded
+ *              on [0.001, t_max] in the sense of rt_scene_occluded, else 1.
+ * params->samples, seed, sample_begin and sample_count mean what they mean for rt_render_features;
+ * tile_world must be 1; the other fields are ignored.  radius must be > 0 or +inf.  RT_E_INVALID: a NaN,
+ * zero or negative radius, a negative chain, tile_world != 1, a bad sample range, a NULL output.  Scenes
+ * with book-2 objects return RT_E_UNSUPPORTED.  rt_render_ao blocks; rt_render_ao_device takes a device
+ * pointer and is asynchronous on `stream` (NULL: the context's stream). */
+int rt_render_ao(rt_ctx* ctx, const rt_camera* cam, const rt_render_params* params, int32_t chain, double radius,
+                 double* ao_host /* [H][W] */);
+int rt_render_ao_device(rt_ctx* ctx, const rt_camera* cam, const rt_render_params* params, int32_t chain,
+                        double radius, double* ao_dev, void* stream);
 
 #ifdef __cplusplus
 }

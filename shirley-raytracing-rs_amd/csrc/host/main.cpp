@@ -18,7 +18,10 @@
 // far: a checkpoint), --resume FILE (continue from such a checkpoint: its sums cover samples [0, N)),
 // --adaptive T (adaptive sampling, rt_render_adaptive: -s is the per-pixel maximum, an 8x8 tile stops when
 // its relative error is <= T; --min-samples N and --adaptive-step N, multiples of --sample-chunk (0 = 4),
-// --noise-floor F; the picture divides every pixel by its own sample count; one GPU, no checkpoints).
+// --noise-floor F; the picture divides every pixel by its own sample count; one GPU, no checkpoints),
+// --ao RADIUS (`inf` accepted) [--ao-chain K]: the ambient-occlusion pass (rt_render_ao) over the frame's
+// samples in place of the colour render, written as a grey picture through the tonemap; one GPU, no
+// checkpoints, no --adaptive / --denoise, no book-2 objects.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -48,6 +51,8 @@ struct Args {
   int min_samples = 16, adaptive_step = 16;
   int denoise = -1, denoise_chain = 8;  // --denoise [N]: à-trous iterations (-1: off)
   bool denoise_variance = false;
+  double ao = 0.0;  // --ao RADIUS: the ambient-occlusion pass in place of the colour render (0: off)
+  int ao_chain = 8;
   double fov = 20.0, focal = 1.0, aperture = 0.001;
   bool night = false, single_threaded = false;
   unsigned long long seed = 0x5EED;
@@ -64,7 +69,8 @@ struct Args {
                "         --seed N --device N --gpus N --partition tiles|samples --bvh reference|sah --sample-chunk N\n"
                "         --dump-accum FILE --progressive K --resume FILE\n"
                "         --adaptive T --min-samples N --adaptive-step N --noise-floor F\n"
-               "         --denoise [N] --denoise-chain K --denoise-variance (with --adaptive)\n");
+               "         --denoise [N] --denoise-chain K --denoise-variance (with --adaptive)\n"
+               "         --ao RADIUS|inf --ao-chain K\n");
   std::exit(2);
 }
 
@@ -291,12 +297,13 @@ int render_scene(const Args& a, const rt_scene_desc* desc, const rt_camera& cam)
     samples = 1;
   }
   if (a.gpus > 1) return render_scene_multi(a, desc, cam, samples);
-  if (a.denoise >= 0)
+  if (a.denoise >= 0 || a.ao > 0.0)
     for (int i = 0; i < desc->n_objects; ++i) {
       const rt_object& o = desc->objects[i];
       if (o.geometry == RT_GEOM_MOVING_SPHERE || o.medium || o.transform) {
-        std::fprintf(stderr, "error: --denoise: the feature pass does not support book-2 objects (moving spheres, "
-                             "media, instance transforms); object %d is one\n", i);
+        std::fprintf(stderr, "error: %s: the %s pass does not support book-2 objects (moving spheres, "
+                             "media, instance transforms); object %d is one\n", a.ao > 0.0 ? "--ao" : "--denoise",
+                     a.ao > 0.0 ? "ambient-occlusion" : "feature", i);
         return 1;
       }
     }
@@ -324,7 +331,24 @@ int render_scene(const Args& a, const rt_scene_desc* desc, const rt_camera& cam)
   std::vector<double> accum;
   std::vector<uint8_t> rgb(n);
   auto t1 = std::chrono::steady_clock::now();
-  if (a.adaptive) {
+  if (a.ao > 0.0) {
+    // the ambient-occlusion pass in place of the colour render: its visibility sums as a grey picture
+    std::vector<double> vis(n / 3);
+    if ((st = rt_render_ao(ctx, &cam, &p, a.ao_chain, a.ao, vis.data()))) {
+      std::fprintf(stderr, "error: --ao: %s\n", rt_last_error(ctx));
+      rt_destroy(ctx);
+      return 1;
+    }
+    accum.resize(n);
+    for (size_t i = 0; i < n; ++i) accum[i] = vis[i / 3];
+    rt_tonemap(accum.data(), cam.image_width, cam.image_height, samples, rgb.data());
+    rt_destroy(ctx);
+    if (sh_write_png(a.output.c_str(), rgb.data(), cam.image_width, cam.image_height)) {
+      std::fprintf(stderr, "error: %s\n", sh_last_error());
+      return 1;
+    }
+    return 0;
+  } else if (a.adaptive) {
     // adaptive sampling: tiles stop at their own sample count, the picture divides by the counts
     rt_adaptive_params ap{};
     ap.min_samples = a.min_samples;
@@ -515,6 +539,11 @@ int main(int argc, char** argv) {
     }
     else if (s == "--denoise-chain") a.denoise_chain = std::atoi(next().c_str());
     else if (s == "--denoise-variance") a.denoise_variance = true;
+    else if (s == "--ao") {  // a radius > 0; strtod reads `inf`
+      a.ao = std::strtod(next().c_str(), nullptr);
+      if (!(a.ao > 0.0)) usage("--ao takes a radius > 0 (or inf)");
+    }
+    else if (s == "--ao-chain") a.ao_chain = std::atoi(next().c_str());
     else if (s == "--partition") {
       const std::string v = next();
       if (v == "tiles") a.partition = RT_PARTITION_TILES;
@@ -548,6 +577,12 @@ int main(int argc, char** argv) {
   if (a.denoise > 8 || a.denoise_chain < 0) usage("--denoise takes 0 to 8 iterations, --denoise-chain K >= 0");
   if (a.denoise_variance && !(a.adaptive && a.denoise >= 0))
     usage("--denoise-variance feeds the moments of an --adaptive frame to --denoise");
+
+  if (a.ao > 0.0 && (a.gpus > 1 || a.progressive > 1 || !a.resume.empty()))
+    usage("--ao renders on one GPU, without --progressive / --resume");
+  if (a.ao > 0.0 && (a.adaptive || a.denoise >= 0)) usage("--ao replaces the colour render: no --adaptive, no --denoise");
+  if (a.ao > 0.0 && !a.dump_accum.empty()) usage("--ao frames are not checkpointed (--dump-accum)");
+  if (a.ao_chain < 0) usage("--ao-chain K >= 0");
 
   sh_scene* scene = nullptr;
   std::string cam_scene = a.scene;

@@ -203,6 +203,15 @@ RT_SIGNATURES = {
     "rt_moments_variance": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "rt_moments_variance_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
                                              C.c_void_p, C.c_void_p]),
+    # ABI 11
+    "rt_scene_occluded": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_void_p,
+                                    C.c_void_p]),
+    "rt_scene_occluded_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_void_p,
+                                           C.c_void_p, C.c_void_p]),
+    "rt_render_ao": (C.c_int, [C.c_void_p, C.POINTER(rt_camera), C.POINTER(rt_render_params), C.c_int32, C.c_double,
+                               C.c_void_p]),
+    "rt_render_ao_device": (C.c_int, [C.c_void_p, C.POINTER(rt_camera), C.POINTER(rt_render_params), C.c_int32,
+                                      C.c_double, C.c_void_p, C.c_void_p]),
 }
 
 # every symbol declared in include/shirley_host.h

@@ -284,6 +284,48 @@ class Device:
         _check(self._h, code)
         return out[:len(r)]
 
+    def occluded(self, rays: np.ndarray, t_min: float = 0.001, t_max=float("inf")) -> np.ndarray:
+        """rt_scene_occluded for rays [n][6] -> uint8 [n]: 1 where some object is hit with t in [t_min, t_max]
+        (exactly where hit(..., traversal="render") reports an object).  `t_max`: a float, or an array [n] of
+        per-ray bounds (a shadow ray's distance to its light)."""
+        r = np.ascontiguousarray(rays, dtype=np.float64).reshape(-1, 6)
+        each = None
+        if np.ndim(t_max) > 0:
+            each = np.ascontiguousarray(t_max, dtype=np.float64).reshape(-1)
+            if len(each) != len(r):
+                raise ValueError("t_max array must hold one bound per ray")
+        out = np.zeros(max(1, len(r)), dtype=np.uint8)
+        _check(self._h, N.rt_lib().rt_scene_occluded(
+            self._h, r.ctypes.data if len(r) else out.ctypes.data, len(r), float(t_min),
+            float("inf") if each is not None else float(t_max),
+            each.ctypes.data if each is not None and len(r) else None, out.ctypes.data))
+        return out[:len(r)]
+
+    def occluded_device(self, rays_ptr: int, n: int, out_ptr: int, t_min: float = 0.001, t_max: float = float("inf"),
+                        t_max_each_ptr: int = 0, stream: int = 0):
+        """rt_scene_occluded_device: device rays [n][6] f64, optional device bounds [n] f64 (0: `t_max` for
+        every ray) -> device uint8 [n]; asynchronous on `stream`."""
+        _check(self._h, N.rt_lib().rt_scene_occluded_device(
+            self._h, C.c_void_p(rays_ptr or None), int(n), float(t_min), float(t_max),
+            C.c_void_p(t_max_each_ptr or None), C.c_void_p(out_ptr or None), C.c_void_p(stream or None)))
+
+    def render_ao(self, camera: N.rt_camera, settings: RenderSettings, chain: int = 8,
+                  radius: float = float("inf")) -> np.ndarray:
+        """rt_render_ao -> [H][W] f64 sums of the 0/1 visibility over the settings' sample range, row 0 = bottom;
+        `chain` as render_features'; `radius`: how far an occluder counts (> 0, inf accepted)."""
+        out = np.zeros((camera.image_height, camera.image_width), dtype=np.float64)
+        p = settings.params()
+        _check(self._h, N.rt_lib().rt_render_ao(self._h, C.byref(camera), C.byref(p), int(chain), float(radius),
+                                                out.ctypes.data))
+        return out
+
+    def render_ao_device(self, camera, settings: RenderSettings, chain: int, radius: float, ao_ptr: int,
+                         stream: int = 0):
+        """rt_render_ao_device: device [H][W] f64 output; asynchronous on `stream`."""
+        p = settings.params()
+        _check(self._h, N.rt_lib().rt_render_ao_device(self._h, C.byref(camera), C.byref(p), int(chain), float(radius),
+                                                       C.c_void_p(ao_ptr or None), C.c_void_p(stream or None)))
+
     def probe(self, rays: np.ndarray, seed: int, sample: int = 0, draw: int = 0):
         """One iteration of ray_color's loop (render.rs:30-46) per ray through the megakernel's device code
         (rt_probe_segment): ray i on the path key (seed, pixel = i, sample, draw) -> rt_probe array
