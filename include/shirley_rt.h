@@ -225,6 +225,11 @@ typedef struct rt_scene_stats {
   /* ABI 9 */
   int32_t hop_pass;     /* 1: the trace kernel runs its hop pass (a reference scene held in LDS with a dielectric
                          * RectBox; SHIRLEY_NO_HOP at upload: 0); frames and counters are the same either way */
+  /* added within ABI 11, in the struct's former tail padding: its size stays 48 bytes and every earlier field keeps
+   * its offset, so RT_ABI_VERSION is unchanged (a caller built before it reads what it read) */
+  int32_t hop_kind;     /* how the hop pass finds a candidate's closest hit: 0 no pass, 1 a visit of the tree's first
+                         * node, 2 the scene's ground stack alone (its rects and RectBoxes under spheres that rest on
+                         * them; SHIRLEY_HOP=root at upload: 1 where 2 would be chosen) */
 } rt_scene_stats;
 
 /* Counters of the last render call (deterministic for a given seed). */

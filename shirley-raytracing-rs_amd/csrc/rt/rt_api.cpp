@@ -424,6 +424,7 @@ int render_window(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, co
     kb.partial = kp.partial;
     kb.unit_counter = kp.unit_counter;
     kb.counters = kp.counters;
+    kb.ground = c->place.hop_kind == 2 ? static_cast<const DGround*>(c->ground.p) : nullptr;
     void* kdev = static_cast<KBlock*>(c->kcam.p) + k;
     HIP_TRY(c, hipMemcpyAsync(kdev, &kb, sizeof(KBlock), hipMemcpyHostToDevice, s));
     kp.kconst = (uint64_t)(uintptr_t)kdev;
@@ -438,7 +439,7 @@ int render_window(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, co
       ks.scene.n_lds_mats = ks.scene.n_lds_texs = 0;
       HIP_TRY(c, launch_split(ks, c->split_nt, c->cu_count, s));
     } else {
-      HIP_TRY(c, launch_trace(kp, (int)nseg, c->place.mk_threads, c->place.hop_pass, s));
+      HIP_TRY(c, launch_trace(kp, (int)nseg, c->place.mk_threads, c->place.hop_kind, s));
     }
     HIP_TRY(c, hipEventRecord(c->pass_ev[2 * k + 1], s));
     if (k == passes - 1) HIP_TRY(c, hipEventRecord(c->ev[1], s));
@@ -503,7 +504,7 @@ int rt_destroy(rt_ctx* c) {
   if (!c) return RT_OK;
   (void)hipSetDevice(c->device);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
-  for (DevBuf* b : {&c->nodes, &c->nodes4, &c->prims, &c->mats, &c->texs, &c->perlin, &c->texels, &c->exts, &c->partial, &c->kcam, &c->shutter0, &c->moments, &c->tile_list, &c->tile_err, &c->dn_a, &c->dn_b, &c->feat,
+  for (DevBuf* b : {&c->nodes, &c->nodes4, &c->prims, &c->mats, &c->texs, &c->perlin, &c->texels, &c->exts, &c->ground, &c->partial, &c->kcam, &c->shutter0, &c->moments, &c->tile_list, &c->tile_err, &c->dn_a, &c->dn_b, &c->feat,
                     &c->accum, &c->counters, &c->unit_counter, &c->wf_pool, &c->wf_iters, &c->packed, &c->gathered,
                     &c->parts, &c->band, &c->digests})
     release(*b);
@@ -541,6 +542,11 @@ int rt_scene_upload(rt_ctx* c, const rt_scene_desc* d, int32_t builder) {
   } else {
     release(c->exts);
   }
+  if (!cs.ground.empty()) {
+    if ((st = up(c->ground, cs.ground))) return st;
+  } else {
+    release(c->ground);
+  }
   if ((st = ensure(c, c->shutter0, 2 * sizeof(double)))) return st;
   HIP_TRY(c, hipMemset(c->shutter0.p, 0, 2 * sizeof(double)));
 
@@ -563,7 +569,7 @@ int rt_scene_upload(rt_ctx* c, const rt_scene_desc* d, int32_t builder) {
   c->place = P;
 
   int bpc = 0;
-  HIP_TRY(c, trace_occupancy(S, P.mk_threads, P.hop_pass, &bpc));
+  HIP_TRY(c, trace_occupancy(S, P.mk_threads, P.hop_kind, &bpc));
   if (bpc < 1) return fail(c, RT_E_UNSUPPORTED, "trace kernel does not fit on a CU (LDS %lld B)", P.stack_bytes);
   c->blocks_per_cu = bpc;
   // wavefront extend block: its own LDS node count, no material tables

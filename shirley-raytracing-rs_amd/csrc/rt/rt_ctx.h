@@ -45,6 +45,7 @@ struct rt_ctx {
   bool have_scene = false;
   rt::DScene scene{};
   DevBuf nodes, nodes4, prims, mats, texs, perlin, texels, exts;
+  DevBuf ground;  // the ground-stack record and its guard bitmap (place.hop_kind == 2; rt_layout.h DGround)
   rt_scene_stats stats{};
   int blocks_per_cu = 0;
   rt::ScenePlacement place;        // the uploaded scene's plan (place.mk_threads: the megakernel block size)

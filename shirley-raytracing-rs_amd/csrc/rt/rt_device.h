@@ -1625,6 +1625,74 @@ __device__ __noinline__ RootHit traverse4_root_ool(const DNode4F* lds_nodes, con
 }
 #endif
 
+// The hop pass of a scene with a ground stack (rt_layout.h DGround, scene_compile.cpp ground_stack; trace.hip
+// HOP = 2): the closest hit among the stack's own primitives G, by one wave-uniform loop over them — RectBoxes,
+// then rects, each with the calls leaf_tests4 makes for such a leaf, so t, the face, the winner and the tie
+// mark are the values traverse4 computes for them (it meets them in another order: the closest hit does not
+// depend on it, and neither does the winner of a tie, tie_takes).  True when that hit is the whole scene's
+// closest hit and a dielectric's: no tie mark, a RectBox face with a y normal, and the conditions under which
+// DESIGN.md §3.1 proves that the reference accepts no sphere at or before it — the origin within the slab,
+// |d.y| and the slope within the record's bounds, and a ray that leaves through the top plane Y doing so in a
+// free cell of the guard bitmap.  False: the outputs mean nothing and the lane traverses as before.
+// Does a ray that starts on face `face` of a RectBox (box_t's numbering: max z, min z, max x, min x, max y, min y)
+// with direction d run into the box?
+__device__ __forceinline__ bool box_inward(int face, v3 d) {
+  const double da = face < 2 ? d.z : (face < 4 ? d.x : d.y);
+  return (face & 1) ? da > 0.0 : da < 0.0;
+}
+typedef __attribute__((address_space(4))) const DGround GGround;
+__device__ __forceinline__ bool ground_hop(const DScene& S, const DPrim* lds_prims, const DMat* mats, GGround* g, v3 o, v3 d,
+                                           double t_min, double& t_best, int& best, int& face_best, bool& guarded) {
+  bool div_ok;  // every |d_i| in face_div's range
+  const v3 inv = inv_dir(d, div_ok);
+  const RaySigns ns = ray_signs(inv);
+  t_best = __builtin_inf();
+  best = -1;
+  face_best = -1;
+  const int n = g->n, n_box = g->n_box;
+#pragma unroll 1
+  for (int i = 0; i < n; ++i) {
+    const int leaf = g->prim[i];
+    const DPrim& pr = lds_prims[leaf];
+    double te, t;
+    if (i < n_box) {
+      double tx;
+      if (!slab_s(pr.p, o, inv, ns, t_min, t_best, te, tx)) {
+        mark_tie<false>(best, near_entry(te, t_best));
+        continue;
+      }
+      const int f = div_ok ? box_t1f(pr.p, o, d, inv, ns, t_min, t_best, te, tx, t) : box_t(pr.p, o, d, t_min, t_best, t, inv, div_ok);
+      if (f >= 0 && tie_takes<false>(S, leaf, best, t, t_best, o, inv, ns, t_min)) { t_best = t; best = leaf; face_best = f; }
+    } else {
+      double b[6];
+      leaf_box(pr, b);
+      if (!slab_s(b, o, inv, ns, t_min, t_best, te)) continue;
+      if (rect_t<0, 2>(pr.p, o, d, t_min, t_best, t, inv, div_ok) && tie_takes<false>(S, leaf, best, t, t_best, o, inv, ns, t_min)) {
+        t_best = t; best = leaf; face_best = -1;
+      }
+    }
+  }
+  guarded = false;
+  if (best < 0 || (best & kTieBit) || face_best < 4) return false;  // (faces 4 / 5: a RectBox's max / min y plane)
+  const DPrim& pb = lds_prims[best];
+  const double ay = fabs(d.y);
+  bool ok = mats[pb.material].kind == RT_MAT_DIELECTRIC && o.y >= g->y_lo && o.y <= g->y_hi && ay >= g->dy_min &&
+            ay <= 0x1p300 && d.x * d.x + d.z * d.z <= g->ratio2 * (d.y * d.y);
+  if (ok && (face_best == 4 ? pb.p[4] : pb.p[1]) == g->y_top) {
+    // leaving through Y: the exit point's cell (the hit record's own point, o + t d)
+    const int nx = g->nx;
+    const int ix = ground_cell(o.x + t_best * d.x, g->x0, nx), iz = ground_cell(o.z + t_best * d.z, g->z0, g->nz);
+    if (ix >= 0 && iz >= 0) {
+      typedef __attribute__((address_space(1))) const uint32_t GBits;
+      const unsigned c = (unsigned)iz * (unsigned)nx + (unsigned)ix;
+      GBits* bits = (GBits*)(uintptr_t)((uint64_t)(uintptr_t)g + sizeof(DGround));
+      guarded = (bits[c >> 5] >> (c & 31u)) & 1u;
+      ok = !guarded;
+    }
+  }
+  return ok;
+}
+
 // Step-wise form for wf_extend4, where a ray's traversal state lives across loop iterations.
 struct Trav4 {
   v3 inv;

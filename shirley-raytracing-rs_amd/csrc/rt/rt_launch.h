@@ -11,8 +11,8 @@
 
 namespace rt {
 // trace.hip
-hipError_t trace_occupancy(const DScene& S, int threads, bool hop, int* blocks_per_cu);
-hipError_t launch_trace(const KParams& p, int blocks, int threads, bool hop, hipStream_t stream);
+hipError_t trace_occupancy(const DScene& S, int threads, int hop, int* blocks_per_cu);
+hipError_t launch_trace(const KParams& p, int blocks, int threads, int hop, hipStream_t stream);
 #ifdef RT_PHASE_TIMING
 void phase_counters_dump();
 #endif

@@ -192,6 +192,43 @@ struct DScene {
   int32_t n_lds_texs;      // textures in LDS (after the Perlin tables)
 };
 
+// The ground stack of a scene (scene_compile.cpp ground_stack): its rect and RectBox
+// primitives G when every other primitive is a sphere resting on or above G's top plane Y.  The megakernel's
+// hop pass (trace.hip, HOP = 2) then finds a candidate's closest hit among G alone and serves it under the
+// record's conditions; the guard bitmap (one bit per kGroundCell x kGroundCell cell of the xz rectangle that
+// starts at (x0, z0), row-major nx x nz, 32 cells per word) follows the record in the same device buffer and
+// marks the cells within kGroundGuard of a sphere's contact point: a ray leaving through Y there is not served.
+constexpr int kGroundMaxPrims = 4;
+constexpr double kGroundCellsPerUnit = 32.0;             // a power of two: the scaling below is exact
+constexpr double kGroundCell = 1.0 / kGroundCellsPerUnit;
+constexpr double kGroundGuard = 1.0 / 32.0;              // epsilon of the proof
+constexpr long long kGroundMaxCells = 128LL * 1024 * 8;  // a guard bitmap of at most 128 KiB
+struct alignas(16) DGround {
+  double y_lo, y_hi;  // a served ray starts in [lowest plane of G - tol, Y + tol]
+  double y_top;       // Y
+  double dy_min;      // ... with dy_min <= |d.y| <= 2^300
+  double ratio2;      // ... and d.x^2 + d.z^2 <= ratio2 d.y^2
+  double x0, z0;      // the guard rectangle's corner (multiples of kGroundCell)
+  int32_t nx, nz;     // its cells (0: no guarded sphere)
+  int32_t n, n_box;   // |G|; prim[0 .. n_box) are its RectBoxes, prim[n_box .. n) its rects
+  int32_t prim[kGroundMaxPrims];
+  int32_t pad[2];
+};
+static_assert(sizeof(DGround) == 96, "DGround layout");
+// The guard cell of a coordinate along one axis of the rectangle (n cells from v0), or -1 outside it (and for a
+// NaN).  One expression for the host, which fills the bitmap, and the device, which reads it: v - v0 rounds
+// once (|error| <= 2^-53 |v - v0|, absorbed by the guard radius' slack, scene_compile.cpp) and the scaling by
+// a power of two is exact.
+#ifdef __HIPCC__
+#define RT_HOST_DEVICE __host__ __device__
+#else
+#define RT_HOST_DEVICE
+#endif
+RT_HOST_DEVICE inline int ground_cell(double v, double v0, int n) {
+  const double q = (v - v0) * kGroundCellsPerUnit;
+  return (q >= 0.0 && q < (double)n) ? (int)q : -1;
+}
+
 struct DCamera {
   int32_t width, height;   // image dims
   int32_t has_lens;
@@ -287,6 +324,7 @@ struct alignas(16) KBlock {
   double* partial;
   unsigned long long* unit_counter;
   DCounters* counters;
+  const DGround* ground;  // the scene's ground stack (the HOP = 2 instances only; else null)
 };
 
 // ---- wavefront engine (wavefront.hip): path state of P slots as structure-of-arrays in HBM ----

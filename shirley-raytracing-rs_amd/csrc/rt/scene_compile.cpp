@@ -37,6 +37,7 @@ SceneTuning tuning_from_env() {
   t.no_lds_mats = getenv("SHIRLEY_NO_LDS_MATS") != nullptr;
   t.no_lds_perlin = getenv("SHIRLEY_NO_LDS_PERLIN") != nullptr;
   t.no_hop = getenv("SHIRLEY_NO_HOP") != nullptr;
+  if (const char* e = getenv("SHIRLEY_HOP")) t.hop_root = std::strcmp(e, "root") == 0;
   if (const char* e = getenv("SHIRLEY_SAH_BOXW")) t.sah_box_weight = atof(e);
   t.sah_binned = getenv("SHIRLEY_SAH_BINNED") != nullptr;
   t.wf_extend2 = getenv("SHIRLEY_WF_EXTEND2") != nullptr;
@@ -568,6 +569,137 @@ void flatten4(const BuiltTree& t, const rt_scene_desc* d, double delta, std::vec
 }
 namespace {
 
+// The ground stack of a compiled scene (rt_layout.h DGround; the proof: DESIGN.md §3.1), or false when the
+// scene has none and the hop pass keeps its first-node visit.  G = the rects and RectBoxes; every test below is
+// an exact binary64 comparison of the values the reference's own leaf boxes hold (rt_device.h leaf_box).
+//   * 1 <= |G| <= kGroundMaxPrims, every rect of G an XZ rect, every other primitive a plain sphere, r > 0
+//     (or one the reference never hits, sphere_never_hit);
+//   * Y = the largest hi_y of G's leaf boxes; every sphere's box starts at c.y - r >= Y;
+//   * every y plane of G is Y itself or at least `gap` below it;
+//   * the bounds the proof's constants assume: coordinates <= 2^20, radii <= 2^10, eta <= 2^-16, m <= 2^-13;
+//   * the guard bitmap has at most kGroundMaxCells cells.
+// Constants (names as in the proof): R = 2^10 the largest |d_xz| / |d.y| of a served ray; reach = the slab's
+// thickness times R + 1, the longest served segment; L^2 = (D + reach)^2 + reach^2 + r_max^2 with D the largest
+// distance from a point of G's extent to a sphere centre; m = 2^-38 L^2, 2^10 times the residual bound
+// 32 * 2^-53 L^2 of a root the reference's sphere test computes; eta = m / (2 r_min), the depth below a sphere's
+// lowest point from which |p - c|^2 - r^2 > m; tol = 2^-40 max(1, |Y|, |lowest plane|).
+// A sphere of radius <= 0 whose leaf box c -+ r (sphere.rs:54-60) is inverted or flat along y: hit2 (aabb.rs:62-79)
+// ends with t1 <= t0 on that axis for every ray with a finite non-zero d.y, so the reference never tests the
+// sphere for such a ray (random_scene holds two: check_fit_ball shrinks a ball below zero where it overlaps).
+bool sphere_never_hit(const double* p) { return p[3] <= 0.0 && p[1] - p[3] >= p[1] + p[3]; }
+bool ground_stack(const std::vector<DPrim>& prims, int n_prims, std::vector<uint32_t>& out) {
+  out.clear();
+  std::vector<int32_t> boxes, rects;
+  double top = -std::numeric_limits<double>::infinity(), low = -top;
+  double ex0 = low, ex1 = top, ez0 = low, ez1 = top, r_min = low, r_max = 0.0;
+  std::vector<double> planes;
+  for (int i = 0; i < n_prims; ++i) {
+    const DPrim& q = prims[i];
+    const double* p = q.p;
+    if (q.kind == kPrimBox) {
+      boxes.push_back(i);
+      planes.push_back(p[1]);
+      planes.push_back(p[4]);
+      top = std::max(top, p[4]);
+      ex0 = std::min(ex0, p[0]), ex1 = std::max(ex1, p[3]), ez0 = std::min(ez0, p[2]), ez1 = std::max(ez1, p[5]);
+    } else if (q.kind == kPrimRectXZ) {
+      rects.push_back(i);
+      planes.push_back(p[4]);
+      top = std::max(top, p[4] + 0.0001);  // (leaf_box: the rect's box is padded along its normal)
+      ex0 = std::min(ex0, p[0]), ex1 = std::max(ex1, p[1]), ez0 = std::min(ez0, p[2]), ez1 = std::max(ez1, p[3]);
+    } else if (q.kind == kPrimSphere) {
+      if (!std::isfinite(p[3])) return false;
+      if (sphere_never_hit(p)) continue;
+      if (!(p[3] > 0.0)) return false;
+      r_min = std::min(r_min, p[3]);
+      r_max = std::max(r_max, p[3]);
+    } else {
+      return false;  // another rect orientation, a moving sphere, an extended primitive
+    }
+  }
+  const size_t n_g = boxes.size() + rects.size();
+  if (n_g < 1 || n_g > (size_t)kGroundMaxPrims) return false;
+  for (double y : planes) low = std::min(low, y);
+  const double big = 0x1p20;
+  if (!(std::fabs(top) <= big && std::fabs(low) <= big && ex0 >= -big && ex1 <= big && ez0 >= -big && ez1 <= big &&
+        ex0 <= ex1 && ez0 <= ez1 && r_max <= 0x1p10))
+    return false;
+  double dist = 0.0;  // D
+  std::vector<const DPrim*> guarded;
+  for (int i = 0; i < n_prims; ++i) {
+    const DPrim& q = prims[i];
+    if (q.kind != kPrimSphere || sphere_never_hit(q.p)) continue;
+    const double* p = q.p;
+    const double lo_y = p[1] - p[3];  // the sphere's leaf box (leaf_box), rounded as the reference rounds it
+    if (!(lo_y >= top) || !(std::fabs(p[0]) <= big && std::fabs(p[1]) <= big && std::fabs(p[2]) <= big)) return false;
+    const double dx = std::max(std::fabs(p[0] - ex0), std::fabs(p[0] - ex1));
+    const double dy = std::max(std::fabs(p[1] - low), std::fabs(p[1] - top));
+    const double dz = std::max(std::fabs(p[2] - ez0), std::fabs(p[2] - ez1));
+    dist = std::max(dist, std::sqrt(dx * dx + dy * dy + dz * dz));
+    if (lo_y - top < kGroundGuard / 2) guarded.push_back(&q);  // (one floating higher needs no guard: §3.1)
+  }
+  const double ratio = 0x1p10, tol = 0x1p-40 * std::max(1.0, std::max(std::fabs(top), std::fabs(low)));
+  const double reach = ((top - low) + 2.0 * tol) * (ratio + 1.0);
+  const double l2 = (dist + reach) * (dist + reach) + reach * reach + r_max * r_max;
+  const double m = 0x1p-38 * l2;
+  const double eta = std::isfinite(r_min) ? m / (2.0 * r_min) : 0.0;
+  // (eta <= the guard radius / (2 R), far below the 1/64 of a floating sphere; m <= half of (guard radius / 2)^2)
+  if (!(eta <= 0x1p-16 && m <= 0x1p-13)) return false;
+  const double gap = 4.0 * eta + 4.0 * tol;
+  for (double y : planes)
+    if (y != top && !(y <= top - gap)) return false;
+
+  DGround g;
+  std::memset(&g, 0, sizeof g);
+  g.y_lo = low - tol;
+  g.y_hi = top + tol;
+  g.y_top = top;
+  g.dy_min = std::max((2.0 * eta + 4.0 * tol) / 0.001, 0x1p-100);  // / the renderer's t_min (render.rs:30)
+  g.ratio2 = ratio * ratio;
+  g.n = (int32_t)n_g;
+  g.n_box = (int32_t)boxes.size();
+  for (size_t i = 0; i < boxes.size(); ++i) g.prim[i] = boxes[i];
+  for (size_t i = 0; i < rects.size(); ++i) g.prim[boxes.size() + i] = rects[i];
+  // the guard bitmap over the guarded contact points' rectangle, two cells of margin
+  size_t words = 0;
+  if (!guarded.empty()) {
+    double cx0 = guarded[0]->p[0], cx1 = cx0, cz0 = guarded[0]->p[2], cz1 = cz0;
+    for (const DPrim* q : guarded) {
+      cx0 = std::min(cx0, q->p[0]), cx1 = std::max(cx1, q->p[0]);
+      cz0 = std::min(cz0, q->p[2]), cz1 = std::max(cz1, q->p[2]);
+    }
+    g.x0 = std::floor(cx0 * kGroundCellsPerUnit - 2.0) * kGroundCell;
+    g.z0 = std::floor(cz0 * kGroundCellsPerUnit - 2.0) * kGroundCell;
+    const double nx = std::ceil((cx1 - g.x0) * kGroundCellsPerUnit + 2.0), nz = std::ceil((cz1 - g.z0) * kGroundCellsPerUnit + 2.0);
+    if (!(nx * nz <= (double)kGroundMaxCells)) return false;
+    g.nx = (int32_t)nx;
+    g.nz = (int32_t)nz;
+    words = ((size_t)g.nx * (size_t)g.nz + 31) / 32;
+  }
+  out.assign(sizeof(DGround) / 4 + words, 0u);
+  std::memcpy(out.data(), &g, sizeof g);
+  uint32_t* bits = out.data() + sizeof(DGround) / 4;
+  // a cell is marked when some point of it lies within the guard radius (with 2^-20 of slack for the cell
+  // index's rounding, ground_cell) of a guarded contact point
+  const double rad = kGroundGuard * (1.0 + 0x1p-20);
+  for (const DPrim* q : guarded) {
+    const double cx = q->p[0], cz = q->p[2];
+    const int i0 = ground_cell(cx, g.x0, g.nx), k0 = ground_cell(cz, g.z0, g.nz);  // (inside by the margin)
+    const int span = (int)std::ceil(rad * kGroundCellsPerUnit) + 1;
+    for (int k = std::max(0, k0 - span); k <= std::min(g.nz - 1, k0 + span); ++k)
+      for (int i = std::max(0, i0 - span); i <= std::min(g.nx - 1, i0 + span); ++i) {
+        const double x_lo = g.x0 + i * kGroundCell, z_lo = g.z0 + k * kGroundCell;
+        const double dx = std::max(0.0, std::max(x_lo - cx, cx - (x_lo + kGroundCell)));
+        const double dz = std::max(0.0, std::max(z_lo - cz, cz - (z_lo + kGroundCell)));
+        if (dx * dx + dz * dz <= rad * rad) {
+          const size_t c = (size_t)k * (size_t)g.nx + (size_t)i;
+          bits[c >> 5] |= 1u << (c & 31);
+        }
+      }
+  }
+  return true;
+}
+
 // Where the blocks keep what (ScenePlacement), from the compiled trees and tables.
 int plan_placement(const rt_scene_desc* d, int32_t placement, const SceneTuning& tune, const BuiltTree& tree,
                    const std::vector<DNode4F>& nodes4, int32_t stack4, float origin_limit, CompiledScene& cs,
@@ -641,6 +773,9 @@ int plan_placement(const rt_scene_desc* d, int32_t placement, const SceneTuning&
     coat = o.geometry == RT_GEOM_RECT_BOX && d->materials[o.material].kind == RT_MAT_DIELECTRIC;
   }
   P.hop_pass = coat && !ext && prims_lds && !tune.no_hop;  // tuning
+  // ... by the scene's ground stack where it has one (SHIRLEY_HOP=root: never), else by a first-node visit
+  P.hop_kind = !P.hop_pass ? 0 : (!tune.hop_root && ground_stack(cs.prims, d->n_objects, cs.ground)) ? 2 : 1;
+  if (P.hop_kind != 2) cs.ground.clear();
 
   // wavefront extend block: its own (larger) stack area, the rest of LDS for nodes
   const long long wf_stack = (long long)wf_extend_lds(0, P.stack_depth);
@@ -664,6 +799,7 @@ int plan_placement(const rt_scene_desc* d, int32_t placement, const SceneTuning&
   cs.stats.wide_block = P.wide ? 1 : 0;
   cs.stats.origin_limit = P.origin_limit;
   cs.stats.hop_pass = P.hop_pass ? 1 : 0;
+  cs.stats.hop_kind = P.hop_kind;
   cs.stats.device_bytes = (int64_t)(cs.nodes.size() * sizeof(DNode) + cs.prims.size() * sizeof(DPrim) +
                                     cs.mats.size() * sizeof(DMat) + cs.texs.size() * sizeof(DTex) +
                                     cs.perlin.size() * sizeof(DPerlin) + cs.texels.size());

@@ -31,6 +31,7 @@ struct SceneTuning {
   bool no_lds_mats = false;     // SHIRLEY_NO_LDS_MATS
   bool no_lds_perlin = false;   // SHIRLEY_NO_LDS_PERLIN
   bool no_hop = false;          // SHIRLEY_NO_HOP
+  bool hop_root = false;        // SHIRLEY_HOP=root: the first-node hop pass where the ground-stack one would run
   double sah_box_weight = 4.0;  // SHIRLEY_SAH_BOXW=<c>
   bool sah_binned = false;      // SHIRLEY_SAH_BINNED
   bool wf_extend2 = false;      // SHIRLEY_WF_EXTEND2
@@ -55,6 +56,7 @@ struct ScenePlacement {
   int split_nt = 0;             // RT_ENGINE_SPLIT: traversal waves per block to try (0: scene not eligible)
   int split_refill = 0;         // SceneTuning.split_refill
   bool hop_pass = false;        // the megakernel runs its instances with the hop pass (trace.hip)
+  int hop_kind = 0;             // ... of which kind (rt_scene_stats.hop_kind): 1 first-node visit, 2 ground stack
 };
 
 // The plan's fields of the megakernel's device scene record.
@@ -83,6 +85,8 @@ struct CompiledScene {
   std::vector<DPerlin> perlin;
   std::vector<uint8_t> texels;
   std::vector<size_t> img_off;
+  // hop_kind 2: the ground-stack record followed by its guard bitmap (rt_layout.h DGround); else empty
+  std::vector<uint32_t> ground;
   // device primitive number -> object index (primitives are numbered in the reference tree's leaf order)
   std::vector<int32_t> prim_object;
   // flattened rotated spheres (flat_object): object index -> RotateY's cos, sin, for rt_scene_hit's u, v

@@ -59,7 +59,8 @@ constexpr int kNarrowWaves = RT_NARROW_WAVES;
 
 // LIST: the launch's tiles come from DWork.tile_list (an adaptive step, adaptive.h) — separate instances, so
 // that every other call runs the code it ran without the list.
-// HOP: the hop pass at the end of the iteration body (below) — compiled only into the scene-in-LDS
+// HOP: the hop pass at the end of the iteration body (below) — 0: none; 1: by a visit of the tree's first node;
+// 2: from the scene's ground stack (ScenePlacement.hop_kind) — compiled only into the scene-in-LDS
 // reference-scene instances that launch_trace picks for a scene with a dielectric RectBox (ScenePlacement.hop_pass),
 // so every other instance keeps its code.
 #ifndef RT_HOP_MIN_LANES
@@ -68,7 +69,20 @@ constexpr int kNarrowWaves = RT_NARROW_WAVES;
 // the ground)
 #define RT_HOP_MIN_LANES 40
 #endif
-template <int THREADS, int MODE, bool EXT, bool LIST = false, bool HOP = false>
+// HOP = 2 (a scene with a ground stack): the lane thresholds of the pass's first run and of its second run,
+// whose candidates are the lanes the first run served: 24 / 16 of a sweep from 16 / 8 to 40 / 32.
+// RT_HOP2_INSIDE = 0 (A/B only) counts every rect / RectBox continuation as a candidate, like HOP = 1: best
+// +2.1 % at 32 / 24 against +4.7 % with the inward-ray filter.
+#ifndef RT_HOP2_INSIDE
+#define RT_HOP2_INSIDE 1
+#endif
+#ifndef RT_HOP2_MIN_LANES_A
+#define RT_HOP2_MIN_LANES_A 24
+#endif
+#ifndef RT_HOP2_MIN_LANES_B
+#define RT_HOP2_MIN_LANES_B 16
+#endif
+template <int THREADS, int MODE, bool EXT, bool LIST = false, int HOP = 0>
 __global__ __launch_bounds__(THREADS, THREADS >= kTraceThreadsWide3 ? 1 : (EXT ? RT_NARROW_WAVES_EXT : kNarrowWaves))
 void trace_kernel(KParams P) {
   extern __shared__ unsigned char lds_raw[];
@@ -402,7 +416,7 @@ void trace_kernel(KParams P) {
     // the same per-lane order as an iteration's steps 1, 3 and 4, so frames and counters are bit-identical
     // with and without the pass.  Any other lane keeps its ray untouched and traverses from the root in the
     // next iteration as before.  Wave-uniform: run only with enough candidates to pay for the wave's trip.
-    if constexpr (HOP) {
+    if constexpr (HOP == 1) {
       static_assert(MODE == kSceneLds && !EXT, "the hop pass is built for the scene-in-LDS reference-scene instances");
       // (candidates by the hit's kind; measured and rejected, DESIGN.md §5: lanes that go on from a dielectric
       // hit, −8 %, and RectBox hits from outside only, no better at any threshold)
@@ -440,6 +454,56 @@ void trace_kernel(KParams P) {
             active = false;  // takes its next sample in the next iteration's step 2
           }
         }
+      }
+      PH_STAMP(kPhTail);
+    }
+    // 5'. the hop pass of a scene with a ground stack (HOP = 2; rt_device.h ground_hop): the same
+    // candidates, but the closest hit comes from the stack's own primitives — at most four, no node visit — and
+    // is served where the stack's conditions prove it the scene's closest hit.  That also decides the upward
+    // hop inside the coat, which no first-node visit can (the spheres' boxes start on the coat's top plane), so
+    // the pass runs twice: the second run's candidates are the lanes the first one served, which turns "coat
+    // bottom from below, coat top from inside" into one iteration.  Each run has its own lane threshold.
+    if constexpr (HOP == 2) {
+      static_assert(MODE == kSceneLds && !EXT, "the hop pass is built for the scene-in-LDS reference-scene instances");
+      bool cand = active && !regen && hit;
+      if (cand) cand = lds_prims[prim].kind != kPrimSphere;
+#if RT_HOP2_INSIDE
+      // (of the lanes that go on from a RectBox face, only those whose new ray runs inside that box — its next
+      // hit is the box's far side unless another primitive of the stack intervenes; one that left the box goes
+      // on to the rect below or to the sky, which the pass does not serve.  A choice of who tries, not of who is
+      // served: DESIGN.md §5)
+      if (cand && face >= 0) cand = box_inward(face, d);
+#endif
+#pragma unroll 1
+      for (int run = 0; run < 2; ++run) {
+        if (__popcll(__ballot(cand)) < (run ? RT_HOP2_MIN_LANES_B : RT_HOP2_MIN_LANES_A)) break;
+        bool serve = false;
+        double t_hop = __builtin_inf();
+        int p_hop = -1, f_hop = -1;
+        if (cand) {
+          if (run) PH_COUNT(28); else PH_COUNT(26);
+          bool guarded;
+          serve = ground_hop(S, lds_prims, mats, (GGround*)kblock(P.kconst)->ground, o, d, 0.001, t_hop, p_hop, f_hop, guarded);
+          if (guarded) PH_COUNT(30);
+        }
+        n_seg += __popcll(__ballot(serve));
+        if (serve) {
+          if (run) PH_COUNT(29); else PH_COUNT(27);
+          const DPrim pr = lds_prims[p_hop];
+          Hit hh;
+          hit_record<false, false>(S, pr, f_hop, o, d, t_hop, rng, seed, hh);
+          const v3 ru = draw_diel(rng, seed);
+          const v3 ud = unit_fast(d);
+          shade_dielectric(mats[pr.material], ru, ud, rng, o, d, hh);  // (att * 1 = att, no emission)
+          if (--depth_left <= 0) {
+            sum = sum + em;
+            active = false;  // takes its next sample in the next iteration's step 2
+          }
+        }
+        cand = serve && active;
+#if RT_HOP2_INSIDE
+        if (cand) cand = box_inward(f_hop, d);
+#endif
       }
       PH_STAMP(kPhTail);
     }
@@ -882,7 +946,7 @@ static int node_mode4(const DScene& S) {
   return S.n_lds_nodes4 >= S.n_nodes4 ? kNodesLds : (S.n_lds_nodes4 == 0 ? kNodesGlobal : kNodesMixed);
 }
 
-template <int THREADS, int MODE, bool EXT, bool HOP = false>
+template <int THREADS, int MODE, bool EXT, int HOP = 0>
 static hipError_t occupancy_impl1(const DScene& S, int* blocks_per_cu) {
   // allow dynamic LDS beyond the 64 KiB default (gfx950 has 160 KiB per CU)
   const size_t lds = trace_lds_bytes(S.n_lds_nodes4, node4_bytes(S.exts != nullptr), S.n_lds_prims, S.n_lds_perlin, S.stack_depth4, THREADS,
@@ -902,7 +966,7 @@ static hipError_t occupancy_impl(const DScene& S, int* blocks_per_cu) {
   return S.exts ? occupancy_impl1<THREADS, MODE, true>(S, blocks_per_cu)
                 : occupancy_impl1<THREADS, MODE, false>(S, blocks_per_cu);
 }
-template <int THREADS, int MODE, bool EXT, bool HOP = false>
+template <int THREADS, int MODE, bool EXT, int HOP = 0>
 static void launch_trace2(const KParams& p, int blocks, size_t lds, hipStream_t stream) {
   if (p.work.tile_list)
     hipLaunchKernelGGL((trace_kernel<THREADS, MODE, EXT, true, HOP>), dim3(blocks), dim3(THREADS), lds, stream, p);
@@ -929,13 +993,14 @@ static hipError_t hit_prepare(const DScene& S) {
 // Kernel instances: the wide block only with the whole (4-wide) BVH in LDS.  Also prepares the
 // rt_scene_hit kernel for the scene.  `hop` (ScenePlacement.hop_pass): the scene-in-LDS reference-scene instances
 // with the hop pass; an error for a scene that runs any other instance.
-hipError_t trace_occupancy(const DScene& S, int threads, bool hop, int* blocks_per_cu) {
+hipError_t trace_occupancy(const DScene& S, int threads, int hop, int* blocks_per_cu) {
   hipError_t e = hit_prepare(S);
   if (e != hipSuccess) return e;
   if (hop && !(threads == kTraceThreadsWide && !S.exts && S.n_lds_prims > 0)) return hipErrorInvalidValue;
   if (threads == kTraceThreadsWide && !S.exts) {  // reference scenes only: book-2 scenes take kTraceThreadsWide3
     if (node_mode4(S) != kNodesLds) return hipErrorInvalidValue;
-    if (hop) return occupancy_impl1<kTraceThreadsWide, kSceneLds, false, true>(S, blocks_per_cu);
+    if (hop == 2) return occupancy_impl1<kTraceThreadsWide, kSceneLds, false, 2>(S, blocks_per_cu);
+    if (hop) return occupancy_impl1<kTraceThreadsWide, kSceneLds, false, 1>(S, blocks_per_cu);
     if (S.n_lds_prims > 0) return occupancy_impl1<kTraceThreadsWide, kSceneLds, false>(S, blocks_per_cu);
     return occupancy_impl1<kTraceThreadsWide, kNodesLds, false>(S, blocks_per_cu);
   }
@@ -951,13 +1016,15 @@ hipError_t trace_occupancy(const DScene& S, int threads, bool hop, int* blocks_p
   }
 }
 
-hipError_t launch_trace(const KParams& p, int blocks, int threads, bool hop, hipStream_t stream) {
+hipError_t launch_trace(const KParams& p, int blocks, int threads, int hop, hipStream_t stream) {
   const size_t lds = trace_lds_bytes(p.scene.n_lds_nodes4, node4_bytes(p.scene.exts != nullptr), p.scene.n_lds_prims, p.scene.n_lds_perlin, p.scene.stack_depth4, threads,
                                      p.scene.n_lds_mats, p.scene.n_lds_texs);
   if (hop && !(threads == kTraceThreadsWide && !p.scene.exts && p.scene.n_lds_prims > 0)) return hipErrorInvalidValue;
   if (threads == kTraceThreadsWide && !p.scene.exts) {
-    if (hop)
-      launch_trace2<kTraceThreadsWide, kSceneLds, false, true>(p, blocks, lds, stream);
+    if (hop == 2)
+      launch_trace2<kTraceThreadsWide, kSceneLds, false, 2>(p, blocks, lds, stream);
+    else if (hop)
+      launch_trace2<kTraceThreadsWide, kSceneLds, false, 1>(p, blocks, lds, stream);
     else if (p.scene.n_lds_prims > 0)
       launch_trace2<kTraceThreadsWide, kSceneLds, false>(p, blocks, lds, stream);
     else
@@ -1154,8 +1221,9 @@ void phase_counters_dump() {
                                 "pop_iter", "segment_iter", "box_iter", "marble_round", "draws_coop_round",
                                 "unit_fetch", "camera_ray", "philox_A", "philox_B", "marble_sin", "hit_record",
                                 "checker_level", "dielectric", "metal", "lambertian", "sky", "diffuse_light",
-                                "reflectance", "traverse4", "publish", "tie_resolve", "hop_candidate", "hop_served"};
-  for (int i = 0; i < 28; ++i)
+                                "reflectance", "traverse4", "publish", "tie_resolve", "hop_candidate", "hop_served",
+                                "hop2_candidate", "hop2_served", "hop_guarded"};
+  for (int i = 0; i < 31; ++i)
     if (h[2 * i + 1])
       fprintf(stderr, "[phase-ev] %-18s lanes %.4g waves %.4g lanes/wave %.2f\n", names[i], (double)h[2 * i],
               (double)h[2 * i + 1], (double)h[2 * i] / (double)h[2 * i + 1]);

@@ -87,7 +87,9 @@ class rt_scene_stats(C.Structure):
                 # ABI 4
                 ("n_nodes4", C.c_int32), ("wide_block", C.c_int32), ("origin_limit", C.c_double),
                 # ABI 9
-                ("hop_pass", C.c_int32)]
+                ("hop_pass", C.c_int32),
+                # the former tail padding (ABI 11, size unchanged)
+                ("hop_kind", C.c_int32)]
 
 
 class rt_counters(C.Structure):
