@@ -581,6 +581,76 @@ int rt_render_ao(rt_ctx* ctx, const rt_camera* cam, const rt_render_params* para
 int rt_render_ao_device(rt_ctx* ctx, const rt_camera* cam, const rt_render_params* params, int32_t chain,
                         double radius, double* ao_dev, void* stream);
 
+/* ---- the scene's light list and the direct-lighting pass ---------------------------
+ * Added within ABI 11, as rt_scene_stats.hop_kind was: the entry points below are purely additive — no
+ * earlier struct, enum or function changes — so RT_ABI_VERSION stays 11.
+ *
+ * Light list.  A listed light is an object, neither medium nor instance (medium == transform == 0), whose
+ * material is RT_MAT_DIFFUSE_LIGHT or RT_MAT_FAIRY_LIGHT with an RT_TEX_SOLID texture and whose geometry is
+ *   RT_GEOM_RECT_XY / YZ / XZ with d1_max - d1_min > 0 and d2_max - d2_min > 0, or
+ *   RT_GEOM_SPHERE with radius > 0.
+ * Lights are listed in object order.  Every other object with one of the two emitter materials — a checker,
+ * Perlin or image texture, a RectBox, a moving sphere, a zero or negative radius, an empty rect, a medium or
+ * an instance — is unlisted: counted, and seen by the pass below only when a camera path lands on it.
+ *   area   rect: (d1_max - d1_min) * (d2_max - d2_min);  sphere: (4 * pi) * (r * r), pi = 3.141592653589793
+ *          (IEEE binary64 products in this order). */
+typedef struct rt_light {
+  int32_t object;    /* index into rt_scene_desc.objects */
+  int32_t geometry;  /* RT_GEOM_* of that object */
+  int32_t emitter;   /* RT_MAT_DIFFUSE_LIGHT or RT_MAT_FAIRY_LIGHT */
+  int32_t pad;
+  double area;
+  double color[3];   /* the solid texture's colour */
+} rt_light;
+/* The uploaded scene's list (built by rt_scene_upload) / the same list from a description, without a device.
+ * *n_lights and *n_unlisted (either may be NULL) receive the counts; out == NULL asks for the counts only,
+ * otherwise it has room for *n_lights records. */
+int rt_scene_lights(rt_ctx* ctx, int32_t* n_lights, int32_t* n_unlisted, rt_light* out);
+int rt_scene_lights_host(const rt_scene_desc* scene, int32_t* n_lights, int32_t* n_unlisted, rt_light* out);
+
+/* Direct lighting: per-pixel SUMS over the call's sample range of what the feature vertex emits (`emission`)
+ * and of a one-light-sample estimate of the light reaching it from the listed lights (`direct`); both
+ * [H][W][3] f64, row 0 = bottom; either may be NULL, not both.  Sample s of pixel p runs on the render's path
+ * key (seed, p, s): rt_render_features's camera ray and dielectric chain (the same `chain` >= 0) to the feature
+ * vertex, where the path's draw counter is D, the hit record is (x, n) and the last ray's direction is d.
+ *   emission  what rt_probe_segment reports as `emitted` there when `emits`: the sky on a miss, the texture
+ *             value of a DiffuseLight, texture value * (dot(n, -d) / |d|) of a FairyLight (any texture kind);
+ *             0 otherwise.
+ *   direct    0 unless the vertex is Lambertian or FairyLight and the scene lists L >= 1 lights.  With `a` the
+ *             renderer's scatter attenuation there (rt_probe.attenuation: the texture value, unit(value) for a
+ *             FairyLight), on the path's draws D, D+1, ...:
+ *     pick      xi0 = draw D;  k = min((int)(xi0 * (double)L), L - 1): light k of the list.
+ *     rect      xi1, xi2 = draws D+1, D+2;  y[d1] = d1_min + xi1 * (d1_max - d1_min),
+ *               y[d2] = d2_min + xi2 * (d2_max - d2_min), y[axis] = offset, with (d1, d2, axis) = (x, y, z) for
+ *               RECT_XY, (y, z, x) for RECT_YZ, (x, z, y) for RECT_XZ (geometry/rect.rs).
+ *     sphere    r = random_in_unit_sphere on draws D+1, ... (three per attempt; each coordinate -1 + 2 * draw,
+ *               accepted when (x*x + y*y) + z*z <= 1);  u = r / sqrt((x*x + y*y) + z*z) per component;
+ *               y = c + radius * u.
+ *     geometry  w = y - x;  d2 = (w.x*w.x + w.y*w.y) + w.z*w.z;  dist = sqrt(d2);
+ *               cx = ((n.x*w.x + n.y*w.y) + n.z*w.z) / dist;
+ *               cy = |w[axis]| / dist for a rect (the reference's emitters radiate from both faces),
+ *               cy = -((u.x*w.x + u.y*w.y) + u.z*w.z) / dist for a sphere (far-side area samples count zero).
+ *     cut       !(cx > 0 && cy > 0): the sample contributes 0 and no shadow ray is traced (a NaN fails too).
+ *     shadow    the sample contributes 0 iff the ray (x, w) is occluded on [0.001, 1 - 2^-20] in the sense of
+ *               rt_scene_occluded.  The interval stops short of the light itself: an occluder closer to the
+ *               light than 2^-20 of the distance between vertex and light sample is ignored.
+ *     value     Le = colour (DiffuseLight) or colour * cy per channel (FairyLight; lighting.rs:59-65 for the ray
+ *               (x, w));  g = ((cx * cy) / d2) * ((area * (double)L) / pi);  direct_c = (a_c * Le_c) * g.
+ *   Only + - * /, a correctly rounded sqrt, comparisons and selects, in the order written (no fused
+ *   multiply-add): a restatement in IEEE binary64 gives the same bits wherever `a` needs no libm function.
+ *   The light sample's density is 1 / (L * area) per unit area, so E[direct] is the vertex's exact direct
+ *   illumination from the listed lights times `a`, and emission + direct has the expectation of rt_render
+ *   with max_depth = 2 where every emitter is listed and the sky is RT_SKY_NONE.
+ * params->samples, seed, sample_begin and sample_count mean what they mean for rt_render_ao; tile_world must
+ * be 1; the other fields are ignored.  Samples are added in order.  RT_E_INVALID: both outputs NULL, a
+ * negative chain, tile_world != 1, a bad sample range.  Scenes with book-2 objects return RT_E_UNSUPPORTED.
+ * rt_render_direct blocks; rt_render_direct_device takes device pointers and is asynchronous on `stream`
+ * (NULL: the context's stream). */
+int rt_render_direct(rt_ctx* ctx, const rt_camera* cam, const rt_render_params* params, int32_t chain,
+                     double* emission_host /* [H][W][3] or NULL */, double* direct_host /* [H][W][3] or NULL */);
+int rt_render_direct_device(rt_ctx* ctx, const rt_camera* cam, const rt_render_params* params, int32_t chain,
+                            double* emission_dev, double* direct_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

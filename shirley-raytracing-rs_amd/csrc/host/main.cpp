@@ -22,6 +22,9 @@
 // --ao RADIUS (`inf` accepted) [--ao-chain K]: the ambient-occlusion pass (rt_render_ao) over the frame's
 // samples in place of the colour render, written as a grey picture through the tonemap; one GPU, no
 // checkpoints, no --adaptive / --denoise, no book-2 objects.
+// --direct [--direct-chain K]: the direct-lighting pass (rt_render_direct) in place of the colour render — the
+// feature vertex's emission plus the one-light-sample estimate from the scene's light list — through the
+// tonemap; the same restrictions as --ao, and not together with it.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -53,6 +56,8 @@ struct Args {
   bool denoise_variance = false;
   double ao = 0.0;  // --ao RADIUS: the ambient-occlusion pass in place of the colour render (0: off)
   int ao_chain = 8;
+  bool direct = false;  // --direct: the direct-lighting pass in place of the colour render
+  int direct_chain = 8;
   double fov = 20.0, focal = 1.0, aperture = 0.001;
   bool night = false, single_threaded = false;
   unsigned long long seed = 0x5EED;
@@ -70,7 +75,8 @@ struct Args {
                "         --dump-accum FILE --progressive K --resume FILE\n"
                "         --adaptive T --min-samples N --adaptive-step N --noise-floor F\n"
                "         --denoise [N] --denoise-chain K --denoise-variance (with --adaptive)\n"
-               "         --ao RADIUS|inf --ao-chain K\n");
+               "         --ao RADIUS|inf --ao-chain K\n"
+               "         --direct --direct-chain K\n");
   std::exit(2);
 }
 
@@ -297,13 +303,14 @@ int render_scene(const Args& a, const rt_scene_desc* desc, const rt_camera& cam)
     samples = 1;
   }
   if (a.gpus > 1) return render_scene_multi(a, desc, cam, samples);
-  if (a.denoise >= 0 || a.ao > 0.0)
+  if (a.denoise >= 0 || a.ao > 0.0 || a.direct)
     for (int i = 0; i < desc->n_objects; ++i) {
       const rt_object& o = desc->objects[i];
       if (o.geometry == RT_GEOM_MOVING_SPHERE || o.medium || o.transform) {
         std::fprintf(stderr, "error: %s: the %s pass does not support book-2 objects (moving spheres, "
-                             "media, instance transforms); object %d is one\n", a.ao > 0.0 ? "--ao" : "--denoise",
-                     a.ao > 0.0 ? "ambient-occlusion" : "feature", i);
+                             "media, instance transforms); object %d is one\n",
+                     a.direct ? "--direct" : a.ao > 0.0 ? "--ao" : "--denoise",
+                     a.direct ? "direct-lighting" : a.ao > 0.0 ? "ambient-occlusion" : "feature", i);
         return 1;
       }
     }
@@ -341,6 +348,23 @@ int render_scene(const Args& a, const rt_scene_desc* desc, const rt_camera& cam)
     }
     accum.resize(n);
     for (size_t i = 0; i < n; ++i) accum[i] = vis[i / 3];
+    rt_tonemap(accum.data(), cam.image_width, cam.image_height, samples, rgb.data());
+    rt_destroy(ctx);
+    if (sh_write_png(a.output.c_str(), rgb.data(), cam.image_width, cam.image_height)) {
+      std::fprintf(stderr, "error: %s\n", sh_last_error());
+      return 1;
+    }
+    return 0;
+  } else if (a.direct) {
+    // the direct-lighting pass in place of the colour render: emission + direct through the tonemap
+    std::vector<double> direct(n);
+    accum.resize(n);
+    if ((st = rt_render_direct(ctx, &cam, &p, a.direct_chain, accum.data(), direct.data()))) {
+      std::fprintf(stderr, "error: --direct: %s\n", rt_last_error(ctx));
+      rt_destroy(ctx);
+      return 1;
+    }
+    for (size_t i = 0; i < n; ++i) accum[i] += direct[i];
     rt_tonemap(accum.data(), cam.image_width, cam.image_height, samples, rgb.data());
     rt_destroy(ctx);
     if (sh_write_png(a.output.c_str(), rgb.data(), cam.image_width, cam.image_height)) {
@@ -544,6 +568,8 @@ int main(int argc, char** argv) {
       if (!(a.ao > 0.0)) usage("--ao takes a radius > 0 (or inf)");
     }
     else if (s == "--ao-chain") a.ao_chain = std::atoi(next().c_str());
+    else if (s == "--direct") a.direct = true;
+    else if (s == "--direct-chain") a.direct_chain = std::atoi(next().c_str());
     else if (s == "--partition") {
       const std::string v = next();
       if (v == "tiles") a.partition = RT_PARTITION_TILES;
@@ -583,6 +609,13 @@ int main(int argc, char** argv) {
   if (a.ao > 0.0 && (a.adaptive || a.denoise >= 0)) usage("--ao replaces the colour render: no --adaptive, no --denoise");
   if (a.ao > 0.0 && !a.dump_accum.empty()) usage("--ao frames are not checkpointed (--dump-accum)");
   if (a.ao_chain < 0) usage("--ao-chain K >= 0");
+
+  if (a.direct && (a.gpus > 1 || a.progressive > 1 || !a.resume.empty()))
+    usage("--direct renders on one GPU, without --progressive / --resume");
+  if (a.direct && (a.adaptive || a.denoise >= 0 || a.ao > 0.0))
+    usage("--direct replaces the colour render: no --adaptive, no --denoise, no --ao");
+  if (a.direct && !a.dump_accum.empty()) usage("--direct frames are not checkpointed (--dump-accum)");
+  if (a.direct_chain < 0) usage("--direct-chain K >= 0");
 
   sh_scene* scene = nullptr;
   std::string cam_scene = a.scene;

@@ -1,0 +1,176 @@
+// direct.hip — rt_render_direct: per-pixel sums of the feature vertex's emission and of a one-light-sample
+// estimate of its direct illumination from the scene's light list (include/shirley_rt.h).
+//
+// direct_kernel is features_kernel's walk (features.hip: one wave per 8x8 tile, one lane per pixel, the sample
+// loop inside the lane, the same camera ray and dielectric chain, the wave's marble for a Perlin albedo, so
+// lanes of an edge tile outside the image stay, idle, for that wave-wide step) followed, at a Lambertian or
+// FairyLight vertex, by direct_light (direct.h), whose shadow ray asks occluded4 as ao_kernel does
+// (occlusion.hip).  The light table is a kernel argument of its own.  No atomics, no inter-wave traffic.
+// Reference scenes only (no book-2 records): EXT = false instances.
+#include <hip/hip_runtime.h>
+
+#include "direct.h"
+#include "rt_launch.h"
+
+namespace rt {
+
+// Block of the scene-in-LDS placements (`wide`), as features.hip's and occlusion.hip's.
+constexpr int kDirectThreadsWide = kTraceThreadsWide;
+
+template <int THREADS, int MODE>
+__global__ __launch_bounds__(THREADS) void direct_kernel(DScene S, DCamera C, uint64_t seed, int s_begin, int s_end,
+                                                         int chain, int tiles_x, int n_tiles,
+                                                         const DLight* __restrict__ lights, int n_lights,
+                                                         double* __restrict__ emission,
+                                                         double* __restrict__ direct) {
+  extern __shared__ unsigned char lds_raw[];
+  const int tid = threadIdx.x;
+  typedef DNode4F N4;
+  N4* lds_nodes = reinterpret_cast<N4*>(lds_raw);
+  DPrim* lds_prims = reinterpret_cast<DPrim*>(lds_raw + (size_t)S.n_lds_nodes4 * sizeof(N4));
+  const DPerlin* lds_perlin = (MODE == kSceneLds && S.n_lds_perlin > 0)
+                                  ? reinterpret_cast<const DPerlin*>(lds_prims + S.n_lds_prims)
+                                  : nullptr;
+  unsigned char* stk_base = lds_raw + (size_t)S.n_lds_nodes4 * sizeof(N4) +
+                            (MODE == kSceneLds ? (size_t)S.n_lds_prims * sizeof(DPrim) +
+                                                     (size_t)S.n_lds_perlin * sizeof(DPerlin) +
+                                                     (size_t)S.n_lds_mats * sizeof(DMat) +
+                                                     (size_t)S.n_lds_texs * sizeof(DTex)
+                                               : 0);
+  unsigned* stk = reinterpret_cast<unsigned*>(stk_base) + tid;
+  stage_nodes4<MODE>(S, lds_nodes, lds_prims);
+  // wave w of the block renders tile blockIdx * (THREADS / 64) + w; lane l its pixel (l % 8, l / 8)
+  const int tile = blockIdx.x * (THREADS / kWave) + tid / kWave;
+  const int lane = tid % kWave;
+  const int px = (tile % tiles_x) * kTile + lane % kTile;
+  const int py = (tile / tiles_x) * kTile + lane / kTile;
+  // (a whole wave past the last tile leaves together; lanes of an edge tile outside the image stay, idle,
+  // for the wave-wide marble)
+  if (tile >= n_tiles) return;
+  const bool active = px < C.width && py < C.height;
+  const uint32_t pix = (uint32_t)py * (uint32_t)C.width + (uint32_t)px;
+  v3 se = V(0.0, 0.0, 0.0), sd = V(0.0, 0.0, 0.0);
+  unsigned visits = 0, ptests = 0;
+#ifdef RT_PHASE_TIMING
+  unsigned long long steps = 0;
+#endif
+  for (int s = s_begin; s < s_end; ++s) {  // wave-uniform
+    Rng rng{pix, (uint32_t)s, 0u, 0u, 0u};
+    v3 o = V(0.0, 0.0, 0.0), d = V(1.0, 1.0, 1.0);
+    bool hit = false, need_pn = false;
+    int prim = -1, face = -1, leaf = -1, mat = 0, ptab = 0, mk = -1;
+    double psc = 0.0;
+    Hit h;
+    h.point = V(0.0, 0.0, 0.0);
+    h.normal = h.point;
+    h.t = h.u = h.v = 0.0;
+    h.front_face = false;
+    if (active) {
+      const double jx = (double)px + rng_next(rng, seed);  // render.rs:60-63
+      const double jy = (double)py + rng_next(rng, seed);
+      camera_ray(C, rng, seed, jx, jy, o, d);
+      int left = chain;
+      for (;;) {  // features_kernel's walk to the feature vertex
+        double t_best = __builtin_inf();
+        face = -1;
+        prim = traverse4<THREADS, MODE, false>(S, lds_nodes, lds_prims, o, d, 0.001, t_best, face, stk, rng, seed,
+                                                    visits, ptests RT_STAT_ARG(steps));
+        hit = prim >= 0;
+        if (!hit) break;
+        const DPrim pr = (MODE == kSceneLds) ? lds_prims[prim] : S.prims[prim];
+        hit_record<false, false>(S, pr, face, o, d, t_best, rng, seed, h);
+        mat = pr.material;
+        mk = S.mats[mat].kind;
+        if (mk != RT_MAT_DIELECTRIC || left <= 0) break;
+        --left;
+        const v3 rs = draw_diel(rng, seed);
+        shade_dielectric(S.mats[mat], rs, unit_fast(d), rng, o, d, h);
+      }
+      if (hit && (mk == RT_MAT_LAMBERTIAN || mk == RT_MAT_FAIRY_LIGHT || mk == RT_MAT_DIFFUSE_LIGHT)) {
+        leaf = resolve_texture(S, S.mats[mat].tex, h.point);
+        const DTex& tx = S.texs[leaf];
+        if (tx.kind == RT_TEX_PERLIN) {
+          need_pn = true;
+          ptab = tx.table;
+          psc = tx.scale;
+        }
+      }
+    }
+    // the wave's marble values (wave-uniform: every lane of the wave is here)
+    const double pn = lds_perlin ? marble_coop((LdsPerlin*)lds_perlin, need_pn, ptab, psc, h.point)
+                                 : marble_coop(S.perlin, need_pn, ptab, psc, h.point);
+    if (active) {
+      v3 em = V(0.0, 0.0, 0.0), dl = V(0.0, 0.0, 0.0);
+      if (!hit) {
+        em = sky_unit(S, unit_fast(d));
+      } else if (leaf >= 0) {
+        v3 a = leaf_texture_value(S, S.texs, leaf, pn, prim, face, h);
+        if (mk == RT_MAT_DIFFUSE_LIGHT) {  // lighting.rs:21-29: emits, never scatters
+          em = a;
+        } else {
+          if (mk == RT_MAT_FAIRY_LIGHT) {  // shade_factor's emission and attenuation (lighting.rs:42-66)
+            const double sc = dot(h.normal, scale(d, -1.0));
+            em = scale(a, sc / len(d));
+            a = unit(a);
+          }
+          if (n_lights > 0)
+            dl = direct_light<THREADS, MODE>(S, lds_nodes, lds_prims, lights, n_lights, rng, seed, h.point, h.normal,
+                                             a, stk, visits, ptests);
+        }
+      }
+      se = se + em;
+      sd = sd + dl;
+    }
+  }
+  if (!active) return;
+  const size_t p = (size_t)py * (size_t)C.width + (size_t)px;
+  if (emission) {
+    emission[p * 3 + 0] = se.x;
+    emission[p * 3 + 1] = se.y;
+    emission[p * 3 + 2] = se.z;
+  }
+  if (direct) {
+    direct[p * 3 + 0] = sd.x;
+    direct[p * 3 + 1] = sd.y;
+    direct[p * 3 + 2] = sd.z;
+  }
+}
+
+template <int THREADS, int MODE>
+static hipError_t launch_direct_1(const DScene& S, const DCamera& C, uint64_t seed, int s_begin, int s_end, int chain,
+                                  const DLight* lights, int n_lights, double* emission, double* direct,
+                                  hipStream_t stream) {
+  const int tiles_x = (C.width + kTile - 1) / kTile, tiles_y = (C.height + kTile - 1) / kTile;
+  const int n_tiles = tiles_x * tiles_y;
+  const int per_block = THREADS / kWave;
+  const int blocks = (n_tiles + per_block - 1) / per_block;
+  const size_t lds = trace_lds_bytes(S.n_lds_nodes4, node4_bytes(false), MODE == kSceneLds ? S.n_lds_prims : 0,
+                                     MODE == kSceneLds ? S.n_lds_perlin : 0, S.stack_depth4, THREADS,
+                                     MODE == kSceneLds ? S.n_lds_mats : 0, MODE == kSceneLds ? S.n_lds_texs : 0);
+  hipError_t e = hipFuncSetAttribute((const void*)direct_kernel<THREADS, MODE>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     (int)lds);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL((direct_kernel<THREADS, MODE>), dim3(blocks), dim3(THREADS), lds, stream, S, C, seed, s_begin, s_end,
+                     chain, tiles_x, n_tiles, lights, n_lights, emission, direct);
+  return hipGetLastError();
+}
+
+// rt_render_direct: block and placement chosen as launch_features does
+hipError_t launch_direct(const DScene& S, bool wide, const DCamera& C, uint64_t seed, int s_begin, int s_end, int chain,
+                         const DLight* lights, int n_lights, double* emission, double* direct, hipStream_t stream) {
+  if (S.exts) return hipErrorInvalidValue;  // (the caller refuses book-2 scenes)
+  if (n_lights > 0 && !lights) return hipErrorInvalidValue;
+  if (wide) {
+    if (S.n_lds_prims > 0)
+      return launch_direct_1<kDirectThreadsWide, kSceneLds>(S, C, seed, s_begin, s_end, chain, lights, n_lights, emission, direct, stream);
+    return launch_direct_1<kDirectThreadsWide, kNodesLds>(S, C, seed, s_begin, s_end, chain, lights, n_lights, emission, direct, stream);
+  }
+  const int mode = S.n_lds_nodes4 >= S.n_nodes4 ? kNodesLds : (S.n_lds_nodes4 == 0 ? kNodesGlobal : kNodesMixed);
+  switch (mode) {
+    case kNodesLds: return launch_direct_1<kHitThreads, kNodesLds>(S, C, seed, s_begin, s_end, chain, lights, n_lights, emission, direct, stream);
+    case kNodesGlobal: return launch_direct_1<kHitThreads, kNodesGlobal>(S, C, seed, s_begin, s_end, chain, lights, n_lights, emission, direct, stream);
+    default: return launch_direct_1<kHitThreads, kNodesMixed>(S, C, seed, s_begin, s_end, chain, lights, n_lights, emission, direct, stream);
+  }
+}
+
+}  // namespace rt

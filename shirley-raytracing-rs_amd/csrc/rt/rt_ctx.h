@@ -46,6 +46,11 @@ struct rt_ctx {
   rt::DScene scene{};
   DevBuf nodes, nodes4, prims, mats, texs, perlin, texels, exts;
   DevBuf ground;  // the ground-stack record and its guard bitmap (place.hop_kind == 2; rt_layout.h DGround)
+  // the scene's light list (rt_scene_lights): the public records, and their device copies (DLight) that
+  // rt_render_direct hands to its kernel as an argument of its own
+  DevBuf lights;
+  std::vector<rt_light> light_list;
+  int32_t n_unlisted_lights = 0;
   rt_scene_stats stats{};
   int blocks_per_cu = 0;
   rt::ScenePlacement place;        // the uploaded scene's plan (place.mk_threads: the megakernel block size)

@@ -1,7 +1,7 @@
 // rt_launch.h — the launch wrappers of the HIP files, as the host side of the C ABI calls them.
 //
 // Included by rt_api.cpp, rt_multi.cpp, rt_denoise.cpp and by the files that define the wrappers (trace.hip,
-// trace_split.hip, wavefront.hip, features.hip, denoise.hip, occlusion.hip), so a changed signature fails to compile where
+// trace_split.hip, wavefront.hip, features.hip, denoise.hip, occlusion.hip, direct.hip), so a changed signature fails to compile where
 // it is changed.
 #pragma once
 
@@ -50,6 +50,9 @@ hipError_t launch_occluded(const DScene& S, bool wide, bool closest, const doubl
                            double t_max, const double* t_max_each, uint8_t* out, hipStream_t stream);
 hipError_t launch_ao(const DScene& S, bool wide, const DCamera& C, uint64_t seed, int s_begin, int s_end, int chain,
                      double radius, double* ao, hipStream_t stream);
+// direct.hip
+hipError_t launch_direct(const DScene& S, bool wide, const DCamera& C, uint64_t seed, int s_begin, int s_end, int chain,
+                         const DLight* lights, int n_lights, double* emission, double* direct, hipStream_t stream);
 // trace_split.hip
 bool split_supported_nt(int nt);
 hipError_t split_prepare(const DScene& S, int nt, int* blocks_per_cu);

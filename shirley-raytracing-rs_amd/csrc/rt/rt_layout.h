@@ -377,4 +377,17 @@ struct WfParams {
   WfIter* it;
 };
 
+// One listed light (scene_compile.cpp list_lights; rt_scene_lights) as the direct-lighting kernel reads it
+// (direct.hip).  Self-contained — the geometry kind, the object's p[6], the area and the solid colour — so it
+// does not depend on how the tree numbers the primitives.  A kernel argument of its own, not a DScene field.
+struct alignas(16) DLight {
+  int32_t geometry;  // RT_GEOM_RECT_XY / YZ / XZ or RT_GEOM_SPHERE
+  int32_t emitter;   // RT_MAT_DIFFUSE_LIGHT or RT_MAT_FAIRY_LIGHT
+  int32_t pad[2];
+  double p[6];       // rt_object.p: rect d1_min d1_max d2_min d2_max offset; sphere cx cy cz radius
+  double area;
+  double color[3];
+};
+static_assert(sizeof(DLight) == 96, "DLight layout");
+
 }  // namespace rt

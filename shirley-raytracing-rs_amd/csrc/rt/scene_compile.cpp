@@ -808,6 +808,48 @@ int plan_placement(const rt_scene_desc* d, int32_t placement, const SceneTuning&
 
 }  // namespace
 
+// The listing rule of include/shirley_rt.h (rt_scene_lights), object by object.
+LightList list_lights(const rt_scene_desc* d) {
+  LightList out;
+  for (int i = 0; i < d->n_objects; ++i) {
+    const rt_object& o = d->objects[i];
+    const rt_material& m = d->materials[o.material];
+    if (m.kind != RT_MAT_DIFFUSE_LIGHT && m.kind != RT_MAT_FAIRY_LIGHT) continue;
+    const rt_texture& t = d->textures[m.texture];
+    const bool rect = o.geometry == RT_GEOM_RECT_XY || o.geometry == RT_GEOM_RECT_YZ || o.geometry == RT_GEOM_RECT_XZ;
+    bool listed = t.kind == RT_TEX_SOLID && !o.medium && !o.transform;
+    double area = 0.0;
+    if (rect) {
+      const double e1 = o.p[1] - o.p[0], e2 = o.p[3] - o.p[2];
+      listed = listed && e1 > 0.0 && e2 > 0.0;
+      area = e1 * e2;
+    } else if (o.geometry == RT_GEOM_SPHERE) {
+      listed = listed && o.p[3] > 0.0;
+      area = (4.0 * 3.141592653589793) * (o.p[3] * o.p[3]);
+    } else {
+      listed = false;
+    }
+    if (!listed) {
+      ++out.n_unlisted;
+      continue;
+    }
+    rt_light l{};
+    l.object = i;
+    l.geometry = o.geometry;
+    l.emitter = m.kind;
+    l.area = area;
+    DLight dl{};
+    dl.geometry = o.geometry;
+    dl.emitter = m.kind;
+    for (int k = 0; k < 6; ++k) dl.p[k] = o.p[k];
+    dl.area = area;
+    for (int k = 0; k < 3; ++k) l.color[k] = dl.color[k] = t.color[k];
+    out.lights.push_back(l);
+    out.dev.push_back(dl);
+  }
+  return out;
+}
+
 int compile_scene(const rt_scene_desc* d, int32_t builder, const SceneTuning& tune, CompiledScene* out,
                   std::string* err) {
   int st = validate(d, err);
@@ -819,6 +861,7 @@ int compile_scene(const rt_scene_desc* d, int32_t builder, const SceneTuning& tu
   *out = CompiledScene{};
   CompiledScene& cs = *out;
   cs.digest = scene_digest(d, builder);  // (of the description as given)
+  cs.lights = list_lights(d);            // (likewise: rt_light.object indexes the caller's objects)
   std::vector<rt_object> flat;
   const rt_scene_desc fd = flat_scene(d, flat);
   for (int i = 0; i < d->n_objects; ++i)

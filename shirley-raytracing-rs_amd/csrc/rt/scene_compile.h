@@ -74,6 +74,16 @@ inline void place_scene(const ScenePlacement& P, DScene& S) {
   S.n_lds_texs = P.n_lds_texs;
 }
 
+// The scene's light list (rt_scene_lights; include/shirley_rt.h has the listing rule): the public records in
+// object order, the device copy of each (the same order) and the count of emitters the rule leaves out.
+struct LightList {
+  std::vector<rt_light> lights;
+  std::vector<DLight> dev;
+  int32_t n_unlisted = 0;
+};
+// Of a validated description.
+LightList list_lights(const rt_scene_desc* d);
+
 // What rt_scene_upload copies to the device and records in the context.
 struct CompiledScene {
   std::vector<DNode> nodes;
@@ -91,6 +101,7 @@ struct CompiledScene {
   std::vector<int32_t> prim_object;
   // flattened rotated spheres (flat_object): object index -> RotateY's cos, sin, for rt_scene_hit's u, v
   std::vector<std::pair<int32_t, std::pair<double, double>>> uv_fixups;
+  LightList lights;
   rt_scene_stats stats{};
   uint64_t digest = 0;
   int32_t n_perlin = 0;

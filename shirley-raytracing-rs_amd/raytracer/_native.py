@@ -125,6 +125,11 @@ class rt_denoise_params(C.Structure):  # ABI 10
                 ("sigma_a", C.c_double), ("sigma_c", C.c_double), ("albedo_floor", C.c_double)]
 
 
+class rt_light(C.Structure):  # the scene's light list (added within ABI 11)
+    _fields_ = [("object", C.c_int32), ("geometry", C.c_int32), ("emitter", C.c_int32), ("pad", C.c_int32),
+                ("area", C.c_double), ("color", _d3)]
+
+
 class rt_bvh_node(C.Structure):
     _fields_ = [("box", _d6), ("leaf", C.c_int32), ("lhs", C.c_int32), ("rhs", C.c_int32), ("pad", C.c_int32)]
 
@@ -214,6 +219,14 @@ RT_SIGNATURES = {
                                C.c_void_p]),
     "rt_render_ao_device": (C.c_int, [C.c_void_p, C.POINTER(rt_camera), C.POINTER(rt_render_params), C.c_int32,
                                       C.c_double, C.c_void_p, C.c_void_p]),
+    # added within ABI 11: the light list and the direct-lighting pass
+    "rt_scene_lights": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(rt_light)]),
+    "rt_scene_lights_host": (C.c_int, [C.POINTER(rt_scene_desc), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                       C.POINTER(rt_light)]),
+    "rt_render_direct": (C.c_int, [C.c_void_p, C.POINTER(rt_camera), C.POINTER(rt_render_params), C.c_int32,
+                                   C.c_void_p, C.c_void_p]),
+    "rt_render_direct_device": (C.c_int, [C.c_void_p, C.POINTER(rt_camera), C.POINTER(rt_render_params), C.c_int32,
+                                          C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 # every symbol declared in include/shirley_host.h

@@ -326,6 +326,35 @@ class Device:
         _check(self._h, N.rt_lib().rt_render_ao_device(self._h, C.byref(camera), C.byref(p), int(chain), float(radius),
                                                        C.c_void_p(ao_ptr or None), C.c_void_p(stream or None)))
 
+    def lights(self):
+        """rt_scene_lights of the uploaded scene -> (list of rt_light in object order, n_unlisted): the emitters
+        render_direct samples, and how many emitters the listing rule leaves out (include/shirley_rt.h)."""
+        n, u = C.c_int32(), C.c_int32()
+        _check(self._h, N.rt_lib().rt_scene_lights(self._h, C.byref(n), C.byref(u), None))
+        out = (N.rt_light * max(1, n.value))()
+        _check(self._h, N.rt_lib().rt_scene_lights(self._h, C.byref(n), C.byref(u), out))
+        return list(out[:n.value]), u.value
+
+    def render_direct(self, camera: N.rt_camera, settings: RenderSettings, chain: int = 8):
+        """rt_render_direct -> (emission, direct): [H][W][3] f64 sums over the settings' sample range, row 0 =
+        bottom, of what the feature vertex emits and of the one-light-sample estimate of its direct
+        illumination from the listed lights; `chain` as render_features'."""
+        shape = (camera.image_height, camera.image_width, 3)
+        em, di = np.zeros(shape, dtype=np.float64), np.zeros(shape, dtype=np.float64)
+        p = settings.params()
+        _check(self._h, N.rt_lib().rt_render_direct(self._h, C.byref(camera), C.byref(p), int(chain), em.ctypes.data,
+                                                    di.ctypes.data))
+        return em, di
+
+    def render_direct_device(self, camera, settings: RenderSettings, chain: int, emission_ptr: int, direct_ptr: int,
+                             stream: int = 0):
+        """rt_render_direct_device: device [H][W][3] f64 outputs (0: not wanted; not both); asynchronous on
+        `stream`."""
+        p = settings.params()
+        _check(self._h, N.rt_lib().rt_render_direct_device(
+            self._h, C.byref(camera), C.byref(p), int(chain), C.c_void_p(emission_ptr or None),
+            C.c_void_p(direct_ptr or None), C.c_void_p(stream or None)))
+
     def probe(self, rays: np.ndarray, seed: int, sample: int = 0, draw: int = 0):
         """One iteration of ray_color's loop (render.rs:30-46) per ray through the megakernel's device code
         (rt_probe_segment): ray i on the path key (seed, pixel = i, sample, draw) -> rt_probe array
