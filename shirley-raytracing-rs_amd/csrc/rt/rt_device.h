@@ -1673,7 +1673,10 @@ __device__ __forceinline__ bool ground_hop(const DScene& S, const DPrim* lds_pri
     }
   }
   guarded = false;
-  if (best < 0 || (best & kTieBit) || face_best < 4) return false;  // (faces 4 / 5: a RectBox's max / min y plane)
+  // (faces 4 / 5: a RectBox's max / min y plane.  A hit at exactly t_min is not served: hit2's strict `t_max <= t_min`
+  // then fails every box tested after the first accepted hit, so of two coplanar primitives of G the reference keeps
+  // the one its own walk meets first — an order this loop does not follow)
+  if (best < 0 || (best & kTieBit) || face_best < 4 || !(t_best > t_min)) return false;
   const DPrim& pb = lds_prims[best];
   const double ay = fabs(d.y);
   bool ok = mats[pb.material].kind == RT_MAT_DIELECTRIC && o.y >= g->y_lo && o.y <= g->y_hi && ay >= g->dy_min &&

@@ -5,15 +5,21 @@
  * included unchanged: aabb_hit2, rect_hit, sphere_hit), with the constants of ground_stack; the exhaustive answer
  * tests every primitive as bbox_tree.rs:60-71 does a leaf (hit2 on its bounding box, then the object, against the
  * running closest), once with G tested first and once with G tested last, so a sphere meets both the largest
- * and the smallest t_max any tree order can give it; a served ray must agree with both.
+ * and the smallest t_max any tree order can give it; a served ray must agree with both (`served_wrong`).  It must
+ * also agree with the reference's own answer — the rhs-first walk (oracle.c tree_hit) of the tree oracle.c builds
+ * from the primitives in file order, which is the scene's object order (`served_wrong_reference`).  That walk also
+ * judges a stack with exact ties inside G (a rect on a RectBox's face, a RectBox twice), which the two orders
+ * cannot: which tied primitive wins depends on the tree's leaf order, the order the device numbers
+ * its primitives in and the serve decision below compares by.  With `ties` the exit status follows the walk alone.
  *
- *   ground_hop_check <prims file> <draws> [seed]
+ *   ground_hop_check <prims file> <draws> [seed [ties]]
  * prims file: one line per primitive, `kind dielectric p0 .. p5` (kind 0 sphere, 3 XZ rect, 4 RectBox; C99 hex
  * floats).  Rays: origins on, between and an ulp or a few either side of G's planes, at and around contact
  * points, near G's edges; directions from straight down to |d.y| = 1e-9 |d|, scaled off unit length, many aimed
- * at a contact point offset by 1e-17 .. 1e-1; hits closer than t_min.  Prints the counts as one JSON line — also
- * how many served answers would differ with the guard bitmap, and with the slope bounds, switched off — and
- * exits 1 when a served ray differs.  Test infrastructure (tests/test_ground_hop.py); -ffp-contract=off. */
+ * at a contact point offset by 1e-17 .. 1e-1; hits closer than t_min (a stack without spheres has no contact
+ * point: its draws are the others).  Prints the counts as one JSON line — also how many served answers would
+ * differ with the guard bitmap, with the slope bounds, and with the refusal of a hit at exactly t_min, switched
+ * off — and exits 1 when a served ray differs.  Test infrastructure (tests/test_ground_hop.py); -ffp-contract=off. */
 #include "../oracle/oracle.c"
 
 #include <stdio.h>
@@ -48,6 +54,39 @@ static double ulps(double x, int k) {
   return x;
 }
 
+/* The reference's own tree over the primitives (oracle.c or_scene_new: constructor.rs:9-36) and every primitive's
+ * place in its leaf order, lhs before rhs — the number the device gives it (scene_compile.cpp reference_ranks),
+ * which ground_stack lists G by and tie_takes compares. */
+static or_scene* g_ref;
+static work_t g_work;
+static int *g_rank, *g_by_rank;
+static void build_reference(void) {
+  rt_object* objs = calloc((size_t)g_n, sizeof *objs);
+  for (int i = 0; i < g_n; ++i) {
+    objs[i].geometry = g_prims[i].kind == 0 ? RT_GEOM_SPHERE : g_prims[i].kind == 3 ? RT_GEOM_RECT_XZ : RT_GEOM_RECT_BOX;
+    for (int k = 0; k < 6; ++k) objs[i].p[k] = g_prims[i].p[k];
+  }
+  rt_scene_desc d;
+  memset(&d, 0, sizeof d);
+  d.n_objects = g_n;
+  d.objects = objs;
+  g_ref = or_scene_new(&d);
+  free(objs);
+  work_init(g_ref, &g_work);
+  g_rank = malloc((size_t)g_n * sizeof *g_rank);
+  g_by_rank = malloc((size_t)g_n * sizeof *g_by_rank);
+  int32_t* stack = malloc((size_t)(g_ref->n_tree + 2) * sizeof *stack);
+  int sp = 0, next = 0;
+  if (g_ref->root >= 0) stack[sp++] = g_ref->root;
+  while (sp > 0) {
+    const node_t* nd = &g_ref->tree[stack[--sp]];
+    if (nd->leaf >= 0) { g_rank[nd->leaf] = next; g_by_rank[next++] = nd->leaf; continue; }
+    stack[sp++] = nd->rhs;  /* (popped after the whole lhs subtree) */
+    stack[sp++] = nd->lhs;
+  }
+  free(stack);
+}
+
 static int never_hit(const double* p) { return p[3] <= 0.0 && p[1] - p[3] >= p[1] + p[3]; }
 static int cell_of(double v, double v0, int n) {  /* rt_layout.h ground_cell */
   const double q = (v - v0) * CELLS;
@@ -59,7 +98,8 @@ static int ground_stack(void) {
   double top = -INFINITY, low = INFINITY, ex0 = INFINITY, ex1 = -INFINITY, ez0 = INFINITY, ez1 = -INFINITY;
   double r_min = INFINITY, r_max = 0.0, planes[8];
   int n_planes = 0, boxes[4], rects[4], nb = 0, nr = 0;
-  for (int i = 0; i < g_n; ++i) {
+  for (int k = 0; k < g_n; ++k) {  /* (in the device's numbering: G is listed boxes first, each kind by rank) */
+    const int i = g_by_rank[k];
     const double* p = g_prims[i].p;
     if (g_prims[i].kind == 4) {
       if (nb + nr == 4) return 0;
@@ -178,6 +218,17 @@ static void exhaustive(const ray_t* r, int g_first, double* t, int* best, int* f
     for (int i = 0; i < g_n; ++i)
       if (in_g(i) == ((pass == 0) == (g_first != 0))) leaf_test(i, r, t, best, face);
 }
+/* the reference's own answer: its rhs-first walk of its own tree (oracle.c tree_hit: bbox_tree.rs:56-91), which
+ * also decides which of several primitives hit at exactly the closest t wins */
+static void reference(const ray_t* r, double* t, int* best, int* face) {
+  hit_t h;
+  int32_t obj = -1;
+  *t = INFINITY; *best = -1; *face = -1;
+  if (!tree_hit(g_ref, &g_work, r, T_MIN, INFINITY, &h, &obj)) return;
+  *t = h.t; *best = obj;
+  /* (RectBox::hit keeps the last of its sides at the closest t, whatever t_max >= t it was called with) */
+  if (g_prims[obj].kind == 4) { double tf; *face = box_hit_face(g_prims[obj].p, r, T_MIN, h.t, &tf); }
+}
 
 /* rt_device.h ground_hop restated: 0 not served; 1 served; the flags say which condition alone refused it */
 static int near_entry(double te, double tb) {
@@ -194,9 +245,9 @@ static double slab_entry(aabb_t b, const ray_t* r, double t_min) {  /* hit2's en
   }
   return t_min;
 }
-static int serve(const ray_t* r, double* t_best, int* best, int* face, int* only_guard, int* only_slope) {
+static int serve(const ray_t* r, double* t_best, int* best, int* face, int* only_guard, int* only_slope, int* only_t_min) {
   int tie = 0;
-  *t_best = INFINITY; *best = -1; *face = -1; *only_guard = *only_slope = 0;
+  *t_best = INFINITY; *best = -1; *face = -1; *only_guard = *only_slope = *only_t_min = 0;
   for (int k = 0; k < g_ng; ++k) {
     const int i = g_g[k];
     const prim_c* q = &g_prims[i];
@@ -212,11 +263,12 @@ static int serve(const ray_t* r, double* t_best, int* best, int* face, int* only
     else { if (!rect_hit(0, 2, q->p, r, T_MIN, *t_best, &h)) continue; t = h.t; }
     if (t == *t_best && *best >= 0) {  /* tie_takes */
       if (tie) continue;
-      if (!(i < *best) && aabb_hit2(leaf_box_of(&g_prims[*best]), r, T_MIN, t)) continue;
+      if (!(g_rank[i] < g_rank[*best]) && aabb_hit2(leaf_box_of(&g_prims[*best]), r, T_MIN, t)) continue;
     }
     *t_best = t; *best = i; *face = f; tie = 0;
   }
   if (*best < 0 || tie || *face < 4 || !g_prims[*best].diel) return 0;
+  const int at_t_min = !(*t_best > T_MIN);  /* (a hit at exactly t_min is not served) */
   const double ay = fabs(r->d.y);
   if (!(r->o.y >= y_lo && r->o.y <= y_hi && ay > 0.0 && ay <= 0x1p300)) return 0;
   const int slope = ay >= dy_min && r->d.x * r->d.x + r->d.z * r->d.z <= ratio2 * (r->d.y * r->d.y);
@@ -228,9 +280,10 @@ static int serve(const ray_t* r, double* t_best, int* best, int* face, int* only
       guarded = (g_bits[c >> 5] >> (c & 31)) & 1u;
     }
   }
-  *only_guard = slope && guarded;
-  *only_slope = !slope && !guarded;
-  return slope && !guarded;
+  *only_guard = slope && guarded && !at_t_min;
+  *only_slope = !slope && !guarded && !at_t_min;
+  *only_t_min = slope && !guarded && at_t_min;
+  return slope && !guarded && !at_t_min;
 }
 
 int main(int argc, char** argv) {
@@ -250,6 +303,8 @@ int main(int argc, char** argv) {
     ++g_n;
   }
   fclose(f);
+  const int ties = argc > 4 && !strcmp(argv[4], "ties");
+  build_reference();
   if (!ground_stack()) { printf("{\"ground_stack\": 0}\n"); return 3; }
   int* sph = malloc(g_n * sizeof *sph), n_sph = 0;
   double pl[8], xlo = INFINITY, xhi = -INFINITY, zlo = INFINITY, zhi = -INFINITY;
@@ -261,11 +316,15 @@ int main(int argc, char** argv) {
     else { pl[n_pl++] = p[4]; xlo = fmin(xlo, p[0]); xhi = fmax(xhi, p[1]); zlo = fmin(zlo, p[2]); zhi = fmax(zhi, p[3]); }
   }
   long served = 0, wrong = 0, wrong_no_guard = 0, wrong_no_slope = 0, refused_guard = 0, refused_slope = 0, top_exits = 0;
-  long sphere_wins = 0;
+  long sphere_wins = 0, wrong_ref = 0, refused_t_min = 0, wrong_no_t_min = 0;
   double worst_rho = 0.0;
   for (long it = 0; it < n; ++it) {
-    const int mode = (int)(next_u64() % 8);
-    const double* sp = g_prims[sph[next_u64() % (uint64_t)n_sph]].p;  /* a sphere: its contact point (sp[0], y_top, sp[2]) */
+    int mode = (int)(next_u64() % 8);
+    if (!n_sph && mode != 0 && mode != 2 && mode != 7) {  /* a stack without spheres: no contact-point draws */
+      static const int other[3] = {0, 2, 7};
+      mode = other[next_u64() % 3];
+    }
+    const double* sp = n_sph ? g_prims[sph[next_u64() % (uint64_t)n_sph]].p : NULL;  /* a sphere: its contact point (sp[0], y_top, sp[2]) */
     ray_t r;
     /* origin height: on a plane, ulps around it, or between two planes */
     const double plane = pl[next_u64() % (uint64_t)n_pl];
@@ -273,7 +332,7 @@ int main(int argc, char** argv) {
     r.o.y = hm == 0 ? plane : hm == 1 ? ulps(plane, (int)(next_u64() % 9) - 4) : hm == 2 ? plane + range(-1e-12, 1e-12)
             : hm == 3 ? range(y_lo, y_hi) : hm == 4 ? plane + (unif() < 0.5 ? -1.0 : 1.0) * logu(1e-15, 1e-3) : plane;
     /* origin xz */
-    if (mode == 0) { r.o.x = range(xlo, xhi); r.o.z = range(zlo, zhi); }
+    if (mode == 0 || (mode == 7 && !sp)) { r.o.x = range(xlo, xhi); r.o.z = range(zlo, zhi); }
     else if (mode == 1) { r.o.x = sp[0]; r.o.z = sp[2]; if (unif() < 0.5) { r.o.x = ulps(r.o.x, (int)(next_u64() % 5) - 2); r.o.z += range(-1e-9, 1e-9); } }
     else if (mode == 2) { const double e = logu(1e-12, 1e-2); r.o.x = (unif() < 0.5 ? xlo : xhi) + range(-e, e); r.o.z = (unif() < 0.5 ? zlo : zhi) + range(-e, e); if (unif() < 0.5) r.o.z = range(zlo, zhi); }
     else { const double rho = mode == 3 ? logu(1e-6, 0.5) : logu(1e-3, 8.0), a = range(0.0, 6.283185307179586); r.o.x = sp[0] + rho * cos(a); r.o.z = sp[2] + rho * sin(a); }
@@ -297,16 +356,25 @@ int main(int argc, char** argv) {
       const double target = pl[next_u64() % (uint64_t)n_pl];
       r.o.y = target - r.d.y * T_MIN * (1.0 + range(-1e-9, 1e-9) * (double)(next_u64() % 3));
     }
-    double t, te; int b, fc, be, fe, og, os;
-    const int sv = serve(&r, &t, &b, &fc, &og, &os);
-    if (!sv && !og && !os) continue;
+    double t, te; int b, fc, be, fe, og, os, ot;
+    const int sv = serve(&r, &t, &b, &fc, &og, &os, &ot);
+    if (!sv && !og && !os && !ot) continue;
     int diff = 0;
     for (int gf = 0; gf < 2; ++gf) {
       exhaustive(&r, gf, &te, &be, &fe);
       diff |= !(be == b && fe == fc && te == t);
     }
     if (fc == 4 && g_prims[b].p[4] == y_top) top_exits += sv || og;
-    if (sv) { ++served; wrong += diff; }
+    if (sv || ot) {
+      if (sv) { ++served; wrong += diff; }
+      reference(&r, &te, &be, &fe);
+      const int dr = !(be == b && fe == fc && te == t);
+      if (sv) wrong_ref += dr;
+      else { ++refused_t_min; wrong_no_t_min += dr; }
+      if (sv && dr && wrong_ref <= 5)
+        fprintf(stderr, "served ray differs from the reference: o %a %a %a d %a %a %a: ground %d face %d t %a, reference %d face %d t %a\n",
+                r.o.x, r.o.y, r.o.z, r.d.x, r.d.y, r.d.z, b, fc, t, be, fe, te);
+    }
     if (og) { ++refused_guard; wrong_no_guard += diff; }
     if (os) { ++refused_slope; wrong_no_slope += diff; }
     if (diff && be >= 0 && g_prims[be].kind == 0) {
@@ -316,13 +384,15 @@ int main(int argc, char** argv) {
         worst_rho = fmax(worst_rho, sqrt(ex * ex + ez * ez));
       }
     }
-    if (sv && diff && wrong <= 5)
+    if (sv && diff && wrong <= 5 && !ties)
       fprintf(stderr, "served ray differs: o %a %a %a d %a %a %a: ground %d face %d t %a, exhaustive %d face %d t %a\n", r.o.x,
               r.o.y, r.o.z, r.d.x, r.d.y, r.d.z, b, fc, t, be, fe, te);
   }
   printf("{\"ground_stack\": 1, \"draws\": %ld, \"served\": %ld, \"served_wrong\": %ld, \"refused_by_guard\": %ld, "
          "\"wrong_without_guard\": %ld, \"refused_by_slope\": %ld, \"wrong_without_slope\": %ld, \"top_exits\": %ld, "
-         "\"sphere_wins\": %ld, \"largest_flip_distance\": %.3g, \"dy_min\": %.3g}\n",
-         n, served, wrong, refused_guard, wrong_no_guard, refused_slope, wrong_no_slope, top_exits, sphere_wins, worst_rho, dy_min);
-  return wrong ? 1 : 0;
+         "\"sphere_wins\": %ld, \"largest_flip_distance\": %.3g, \"dy_min\": %.3g, \"served_wrong_reference\": %ld, "
+         "\"refused_at_t_min\": %ld, \"wrong_reference_without_t_min\": %ld}\n",
+         n, served, wrong, refused_guard, wrong_no_guard, refused_slope, wrong_no_slope, top_exits, sphere_wins, worst_rho, dy_min,
+         wrong_ref, refused_t_min, wrong_no_t_min);
+  return (wrong_ref || (wrong && !ties)) ? 1 : 0;
 }

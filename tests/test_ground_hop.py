@@ -2,14 +2,17 @@
 
 tests/ground_hop_check.c restates the pass's serve decision from the oracle's own functions and compares every
 served ray with the exhaustive closest hit over all primitives, by the reference's rules, on random_scene's
-primitives for three seeds; tools/ground_stack prints the kind of hop pass scene compilation chooses and checks the
-guard bitmap it builds by brute force."""
+primitives for three seeds and on the synthetic ground stacks of tests/hop_scenes.py — there also with the walk of
+the reference's own tree, which judges the stacks that hold exact ties; tools/ground_stack prints the kind of hop
+pass scene compilation chooses and checks the guard bitmap it builds by brute force."""
 import json
 import os
 import subprocess
 
 import pytest
 
+import hop_scenes as HS
+import oracle_lib as O
 import raytracer as rt
 from raytracer import _native as N
 
@@ -22,26 +25,25 @@ SEEDS = (SEED, 1, 7)
 DRAWS = 700_000  # per seed: 2.1 M rays in all
 
 
-def write_prims(scene, path):
-    """One line per primitive of a finalized scene: kind, dielectric, p0 .. p5 as hex floats."""
-    d = scene.desc
-    kinds = {N.RT_GEOM_SPHERE: 0, N.RT_GEOM_RECT_XZ: 3, N.RT_GEOM_RECT_BOX: 4}
-    with open(path, "w") as f:
-        for i in range(d.n_objects):
-            o = d.objects[i]
-            diel = int(d.materials[o.material].kind == N.RT_MAT_DIELECTRIC)
-            f.write(" ".join([str(kinds[o.geometry]), str(diel)] + [float(o.p[k]).hex() for k in range(6)]) + "\n")
+write_prims = HS.write_prims
+SCENE_DRAWS = 300_000  # per synthetic stack
 
 
-def test_no_served_ray_differs_from_the_exhaustive_closest_hit(tmp_path):
+@pytest.fixture(scope="module")
+def checker(tmp_path_factory):
+    exe = str(tmp_path_factory.mktemp("ground_hop_check") / "ground_hop_check")
+    subprocess.run(["gcc", "-O2", "-ffp-contract=off", "-w", "-o", exe, os.path.join(REPO, "tests", "ground_hop_check.c"),
+                    "-lm", "-lpthread"], check=True, timeout=300)
+    return exe
+
+
+def test_no_served_ray_differs_from_the_exhaustive_closest_hit(checker, tmp_path):
     """Zero served rays whose ground-only answer differs from the exhaustive one in primitive, face or t, over
     2.1 M adversarial draws; and the check bites: with the guard bitmap switched off some would differ (rays that
     leave the coat within ~5e-8 of a contact point, where the reference's sphere root wins or ties), and so would
     some with the slope bounds off.  Measured: served 67 892 of 300 000 draws, 7 440 wrong without the guard, 36
     without the slope bounds, largest flip distance 4.8e-8 (seed 0x5EED)."""
-    exe = str(tmp_path / "ground_hop_check")
-    subprocess.run(["gcc", "-O2", "-ffp-contract=off", "-w", "-o", exe, os.path.join(REPO, "tests", "ground_hop_check.c"),
-                    "-lm", "-lpthread"], check=True, timeout=300)
+    exe = checker
     procs = []
     for seed in SEEDS:
         path = str(tmp_path / f"prims_{seed}.txt")
@@ -54,11 +56,104 @@ def test_no_served_ray_differs_from_the_exhaustive_closest_hit(tmp_path):
         print(f"seed {seed:#x}: {out.strip()} {err.strip()}")
         r = json.loads(out)
         assert p.returncode == 0 and r["ground_stack"] == 1 and r["draws"] == DRAWS
-        assert r["served_wrong"] == 0
+        assert r["served_wrong"] == 0 and r["served_wrong_reference"] == 0
         assert r["served"] > DRAWS // 10 and r["top_exits"] > DRAWS // 20  # the draws do reach the pass
         for k in total:
             total[k] += r[k]
     assert total["wrong_without_guard"] > 0 and total["wrong_without_slope"] > 0
+
+
+@pytest.fixture(scope="module")
+def stack_checks(checker, tmp_path_factory):
+    """ground_hop_check's counts on every kind-2 stack of tests/hop_scenes.py, all at once (about a second each);
+    the tied stacks under `ties`, where the exit status follows the reference's walk alone."""
+    tmp = tmp_path_factory.mktemp("stack_checks")
+    procs = {}
+    for name in HS.KIND2:
+        path = str(tmp / (name + ".prims"))
+        write_prims(HS.scene(name), path)
+        procs[name] = subprocess.Popen([checker, path, str(SCENE_DRAWS), "7"] + (["ties"] if name in HS.TIED else []),
+                                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
+    res = {}
+    for name, p in procs.items():
+        out, err = p.communicate(timeout=600)
+        print(f"{name}: rc {p.returncode} {out.strip()} {err.strip()}")
+        res[name] = (p.returncode, json.loads(out))
+    return res
+
+
+@pytest.mark.parametrize("name", HS.KIND2)
+def test_no_served_ray_differs_on_a_synthetic_stack(stack_checks, name):
+    """300 000 draws per stack: no served ray differs from the closest hit of the reference's own walk of its own
+    tree (oracle.c tree_hit) in primitive, face or t, and the draws do reach the pass.  On a tie-free stack the served
+    rays also agree with the exhaustive answer under both test orders (served_wrong), as on random_scene.
+
+    The tied stacks are judged by the reference's walk alone.  There every downward exit from the coat is an exact
+    tie between two primitives of G, which the pass decides by tie_takes' rank rule; the two-order
+    answer differs whenever the order it tries is not the reference's — 15 420 of coplanar_br's 30 397 served rays,
+    all 29 470 of twin_coats' — while the reference's walk, whose leaf order the checker takes from the tree
+    oracle.c builds, agrees with every one of them.
+
+    The rays at t == t_min (39 of 400 000 draws on coplanar_rb before this check existed, 31 of this test's
+    300 000 when such a hit was still served): the
+    origin lies exactly 0.001 |d.y| above the plane the rect shares with the coat's lower face.  hit2's `t_max <=
+    t_min` is strict, so once a hit at t_min is accepted the box of every leaf tested later fails, and the first leaf
+    the walk meets keeps the hit, whatever its rank.  In coplanar_rb the reference's tree meets the coat first, as
+    the pass's loop does (RectBoxes before rects): those 31 came from the checker, whose G-first order tests the rect
+    first.  In coplanar_br the reference meets the rect first: there the pass was wrong (28 of 300 000 draws served
+    the coat's face where the reference returns the rect).  ground_hop now refuses a hit at exactly t_min;
+    wrong_reference_without_t_min counts what it would serve wrongly without that, and must stay above zero for the
+    check to bite."""
+    rc, r = stack_checks[name]
+    assert r["ground_stack"] == 1 and r["draws"] == SCENE_DRAWS
+    assert r["served_wrong_reference"] == 0 and rc == 0
+    if name in HS.TIE_FREE:
+        assert r["served_wrong"] == 0
+    # (a tied stack: where the rect is the earlier leaf it wins every downward exit from the coat, and a rect's hit
+    # is never served; the draws' d.y is of either sign with equal chance, so at most half of what a tie-free stack
+    # serves is lost — coplanar_rb served 19 974 of 400 000 draws before this check existed, under one in twenty)
+    assert r["served"] > SCENE_DRAWS // (20 if name in HS.TIE_FREE else 40)
+    if name == "coplanar_br":
+        assert r["refused_at_t_min"] > 0 and r["wrong_reference_without_t_min"] > 0
+    if name == "twin_coats":
+        assert r["served_wrong"] > 0  # (the two-order demand cannot judge a tie: why the reference's walk is here)
+    if HS.RECORD[name][3] and name != "rect_top":
+        assert r["refused_by_guard"] > 0 and r["wrong_without_guard"] > 0
+    else:  # (no guarded sphere; rect_top's top plane is a rect's box, and only a RectBox face is ever served)
+        assert r["refused_by_guard"] == 0
+
+
+def coat_tiles(finalized, osc, cam):
+    """How many of a 32x32 frame's sixteen 8x8 tiles hold at least 48 pixels whose sample-0 primary ray (or_pixel_ray)
+    has the front (+y) face of a dielectric RectBox as its closest hit in the oracle."""
+    d = finalized.desc
+    tiles = [[0] * 4 for _ in range(4)]
+    for py in range(32):
+        for px in range(32):
+            ray = O._d6()
+            O.lib().or_pixel_ray(cam, HS.SEED, px, py, 0, ray)
+            h = osc.hit(list(ray))
+            if not h.hit:
+                continue
+            o = d.objects[h.object]
+            tiles[py // 8][px // 8] += (o.geometry == N.RT_GEOM_RECT_BOX and d.materials[o.material].kind == N.RT_MAT_DIELECTRIC
+                                        and bool(h.front_face) and h.normal[1] == 1.0 and ray[4] < 0.0)
+    return sum(n >= 48 for row in tiles for n in row)
+
+
+@pytest.mark.parametrize("name", HS.NAMES)
+def test_frames_hold_hop_candidates(name):
+    """The frames tests/test_gpu_hop_scenes.py renders do run the pass: in at least 8 of a frame's 16 tiles (a tile is
+    a wave) 48 of the 64 first hits are on a glass coat's top face, by the oracle alone — those lanes are hop
+    candidates after their first segment, and the pass needs 24 (ground stack) or 40 (first node) candidate lanes
+    in a wave.  Measured: down 12 / low 8 with the balls on the coat, 12 / 16 floating, 16 / 16 bare, rect_top
+    12 / 16 (its `down` camera off the balls: hop_scenes.CAMERA_XZ)."""
+    sc = HS.scene(name)
+    osc = O.OracleScene(sc)
+    for cam_name, cam in HS.cameras(name).items():
+        n = coat_tiles(sc, osc, cam)
+        print(f"{name} {cam_name}: {n} of 16 tiles")
+        assert n >= 8, (name, cam_name)
 
 
 def variant(edit):
@@ -125,10 +220,12 @@ def modes(tmp_path_factory):
     subprocess.run(["g++"] + flags + ["-Wa,-I," + os.path.join(PKG, "assets"), "-o", exe] + srcs + ["-lz", "-ldl"], check=True,
                    timeout=900)
     cases = list(BUILTIN)
-    for name, edit in FILES.items():
+    texts = {name: variant(edit) for name, edit in FILES.items()}
+    texts.update({name: HS.scene_json(name) for name in HS.NAMES})
+    for name, text in texts.items():
         path = str(tmp / (name + ".json"))
         with open(path, "w") as f:
-            f.write(variant(edit))
+            f.write(text)
         cases.append("@" + path)
     env = {k: v for k, v in os.environ.items() if not k.startswith("SHIRLEY_")}
     out = subprocess.run([exe] + cases, check=True, capture_output=True, text=True, env=env, timeout=300).stdout
@@ -161,3 +258,23 @@ def test_the_guard_bitmap_against_brute_force(modes, case):
     r = modes[case]
     assert r["cells_wrong"] == 0 and r["points_free"] == 0
     assert 0 < r["cells_marked"] < r["nx"] * r["nz"] // 20 and r["guard_bytes"] <= 128 * 1024
+
+
+@pytest.mark.parametrize("name", HS.NAMES)
+def test_the_mode_chosen_for_a_synthetic_stack(modes, name):
+    """tests/hop_scenes.py: the kind, and for kind 2 the record — how many primitives and boxes, the top plane (a
+    raised rect's padded box for rect_top), a brute-force-clean guard bitmap of 124 x 36 cells, or none at all (no
+    cell, no byte) where no sphere comes within the guard's reach of the top plane."""
+    r = modes[name]
+    kind = HS.KIND[name]
+    assert r["hop_kind"] == kind and r["hop_pass"] == 1
+    if kind != 2:
+        return
+    n, n_box, y_top, guarded = HS.RECORD[name]
+    assert (r["n"], r["n_box"], r["y_top"]) == (n, n_box, y_top)
+    assert r["cells_wrong"] == 0 and r["points_free"] == 0
+    if guarded:
+        assert (r["nx"], r["nz"]) == HS.GUARD_CELLS and r["guarded_spheres"] == 6
+        assert 0 < r["cells_marked"] and 0 < r["guard_bytes"] <= 128 * 1024
+    else:
+        assert (r["nx"], r["nz"], r["guard_bytes"], r["guarded_spheres"], r["cells_marked"]) == (0, 0, 0, 0, 0)
