@@ -651,6 +651,64 @@ int rt_render_direct(rt_ctx* ctx, const rt_camera* cam, const rt_render_params* 
 int rt_render_direct_device(rt_ctx* ctx, const rt_camera* cam, const rt_render_params* params, int32_t chain,
                             double* emission_dev, double* direct_dev, void* stream);
 
+/* ---- the light-sampling path integrator --------------------------------------------
+ * Added within ABI 11 like the light list: purely additive, RT_ABI_VERSION stays 11.
+ *
+ * rt_render_nee is rt_render's path with one light sample (the estimator of rt_render_direct above) at every
+ * Lambertian / FairyLight vertex, and a weight on the emission that the vertex's own scatter then lands on.
+ * Output: rt_render's layout — [H][W][3] f64 SUMS over the call's sample range, row 0 = bottom; rt_tonemap and
+ * rt_denoise apply unchanged.  params->samples, max_depth, seed, sample_begin and sample_count mean what they
+ * mean for rt_render; tile_world must be 1; engine, sample_chunk and scratch_mb are ignored.  Each pixel's
+ * samples are added in order.  max_depth <= 0 gives zero sums.
+ *
+ * Sample s of pixel p runs on the render's path key (seed, p, s) and starts with the render's camera ray.
+ * Segments are numbered k = 1 ... max_depth; att = (1, 1, 1), rad = (0, 0, 0); L = the number of listed
+ * lights.  Segment k does what rt_probe_segment returns for the current ray when called with the path's
+ * running draw counter: the closest hit on [0.001, inf), the record (t, point, n_hit, front_face), `emitted`,
+ * and `scatter` (attenuation a, next ray (x, d')) on the renderer's own draws.
+ *   miss        rad += att * sky (per channel); the path ends.  A sky is never listed.
+ *   emission    a hit that emits: rad += (att * emitted) * ws (per channel, in this order), where
+ *               listed(hit) = the hit object is light j of the list, and it is a rect or the hit is front_face;
+ *               ws = 1 unless the previous vertex took a light sample and listed(hit);
+ *               if both hold and RT_NEE_MIS is clear: ws = 0;
+ *               if both hold and RT_NEE_MIS is set, with d the segment's ray direction and t its hit parameter:
+ *                 ld2 = (d.x*d.x + d.y*d.y) + d.z*d.z;  ld = sqrt(ld2);
+ *                 cy = -((n_hit.x*d.x + n_hit.y*d.y) + n_hit.z*d.z) / ld;  d2 = (t*t) * ld2;
+ *                 gs = ((cx_prev * cy) / d2) / pi;  pl = 1.0 / (area_j * (double)L);  ws = gs / (pl + gs);
+ *                 ws = 1 when !(cx_prev > 0 && cy > 0).
+ *               (A sphere light seen from inside: light sampling gives such a vertex nothing, cy <= 0 there, so
+ *               the scatter keeps that emission in full.)
+ *   no scatter  the path ends.
+ *   light       taken iff the vertex material is Lambertian or FairyLight, L >= 1 and k < max_depth (it stands
+ *   sample      for segment k + 1's emission, so the last vertex takes none), on the path's draws after the
+ *               scatter's own: rt_render_direct's estimator at (x, n) = the record with a = the scatter
+ *               attenuation — the same pick, rect or sphere sample, w, d2, dist, cx, cy, the cut
+ *               !(cx > 0 && cy > 0) before any ray, the shadow ray (x, w) on [0.001, 1 - 2^-20], Le.
+ *               value_c = (a_c * Le_c) * g with
+ *                 RT_NEE_MIS clear: g = ((cx * cy) / d2) * ((area * (double)L) / pi);
+ *                 RT_NEE_MIS set:   gs = ((cx * cy) / d2) / pi;  pl = 1.0 / (area * (double)L);  g = gs / (pl + gs).
+ *               rad += att * value (per channel).  Remembered for the next hit: that a sample was taken (cut and
+ *               occluded ones included) and cx_prev = ((n.x*d'.x + n.y*d'.y) + n.z*d'.z) / sqrt(len2(d')) with
+ *               len2(d') = (d'.x*d'.x + d'.y*d'.y) + d'.z*d'.z.  Metal and dielectric vertices take no
+ *               sample, so the next hit's ws is 1.
+ *   continue    att = att * a (per channel); the next ray is the scatter's; the next segment's draws follow the
+ *               light sample's.
+ * The sample's value is rad.  Only + - * /, a correctly rounded sqrt, comparisons and selects, in the order
+ * written (no fused multiply-add).
+ * Why it is unbiased: the Lambertian scatter has solid-angle density cx / pi, which is gs in area measure at the
+ * light; the light sample's area density is pl; the weights are the balance heuristic (the ws = 0 form hands the
+ * whole contribution to the light sample).  The expectation equals rt_render's at the same max_depth, up to the
+ * shadow interval's 2^-20 gap; unlisted emitters and the sky are never re-weighted.  With RT_NEE_MIS every
+ * light term is bounded by a * Le, so area sampling's 1 / distance^4 outliers are gone.
+ * RT_E_INVALID: unknown flag bits, tile_world != 1, a bad sample range, a NULL output.  Scenes with book-2
+ * objects return RT_E_UNSUPPORTED.  rt_render_nee blocks; rt_render_nee_device takes a device pointer and is
+ * asynchronous on `stream` (NULL: the context's stream). */
+enum { RT_NEE_MIS = 1 }; /* flags */
+int rt_render_nee(rt_ctx* ctx, const rt_camera* cam, const rt_render_params* params, int32_t flags,
+                  double* accum_host /* [H][W][3] */);
+int rt_render_nee_device(rt_ctx* ctx, const rt_camera* cam, const rt_render_params* params, int32_t flags,
+                         double* accum_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

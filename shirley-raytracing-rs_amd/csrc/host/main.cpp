@@ -25,6 +25,9 @@
 // --direct [--direct-chain K]: the direct-lighting pass (rt_render_direct) in place of the colour render — the
 // feature vertex's emission plus the one-light-sample estimate from the scene's light list — through the
 // tonemap; the same restrictions as --ao, and not together with it.
+// --nee [--nee-mis 0|1]: the light-sampling path integrator (rt_render_nee; --nee-mis 1, the default, weights
+// light sample and scatter by the balance heuristic) in place of the colour render, with the usual -s / -m;
+// the same restrictions as --direct, and not together with it.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -58,6 +61,8 @@ struct Args {
   int ao_chain = 8;
   bool direct = false;  // --direct: the direct-lighting pass in place of the colour render
   int direct_chain = 8;
+  bool nee = false;  // --nee: the light-sampling path integrator in place of the colour render
+  int nee_mis = 1;
   double fov = 20.0, focal = 1.0, aperture = 0.001;
   bool night = false, single_threaded = false;
   unsigned long long seed = 0x5EED;
@@ -76,7 +81,8 @@ struct Args {
                "         --adaptive T --min-samples N --adaptive-step N --noise-floor F\n"
                "         --denoise [N] --denoise-chain K --denoise-variance (with --adaptive)\n"
                "         --ao RADIUS|inf --ao-chain K\n"
-               "         --direct --direct-chain K\n");
+               "         --direct --direct-chain K\n"
+               "         --nee --nee-mis 0|1\n");
   std::exit(2);
 }
 
@@ -303,14 +309,14 @@ int render_scene(const Args& a, const rt_scene_desc* desc, const rt_camera& cam)
     samples = 1;
   }
   if (a.gpus > 1) return render_scene_multi(a, desc, cam, samples);
-  if (a.denoise >= 0 || a.ao > 0.0 || a.direct)
+  if (a.denoise >= 0 || a.ao > 0.0 || a.direct || a.nee)
     for (int i = 0; i < desc->n_objects; ++i) {
       const rt_object& o = desc->objects[i];
       if (o.geometry == RT_GEOM_MOVING_SPHERE || o.medium || o.transform) {
         std::fprintf(stderr, "error: %s: the %s pass does not support book-2 objects (moving spheres, "
                              "media, instance transforms); object %d is one\n",
-                     a.direct ? "--direct" : a.ao > 0.0 ? "--ao" : "--denoise",
-                     a.direct ? "direct-lighting" : a.ao > 0.0 ? "ambient-occlusion" : "feature", i);
+                     a.nee ? "--nee" : a.direct ? "--direct" : a.ao > 0.0 ? "--ao" : "--denoise",
+                     a.nee ? "light-sampling" : a.direct ? "direct-lighting" : a.ao > 0.0 ? "ambient-occlusion" : "feature", i);
         return 1;
       }
     }
@@ -365,6 +371,21 @@ int render_scene(const Args& a, const rt_scene_desc* desc, const rt_camera& cam)
       return 1;
     }
     for (size_t i = 0; i < n; ++i) accum[i] += direct[i];
+    rt_tonemap(accum.data(), cam.image_width, cam.image_height, samples, rgb.data());
+    rt_destroy(ctx);
+    if (sh_write_png(a.output.c_str(), rgb.data(), cam.image_width, cam.image_height)) {
+      std::fprintf(stderr, "error: %s\n", sh_last_error());
+      return 1;
+    }
+    return 0;
+  } else if (a.nee) {
+    // the light-sampling path integrator in place of the colour render: the same sums, through the tonemap
+    accum.resize(n);
+    if ((st = rt_render_nee(ctx, &cam, &p, a.nee_mis ? RT_NEE_MIS : 0, accum.data()))) {
+      std::fprintf(stderr, "error: --nee: %s\n", rt_last_error(ctx));
+      rt_destroy(ctx);
+      return 1;
+    }
     rt_tonemap(accum.data(), cam.image_width, cam.image_height, samples, rgb.data());
     rt_destroy(ctx);
     if (sh_write_png(a.output.c_str(), rgb.data(), cam.image_width, cam.image_height)) {
@@ -570,6 +591,11 @@ int main(int argc, char** argv) {
     else if (s == "--ao-chain") a.ao_chain = std::atoi(next().c_str());
     else if (s == "--direct") a.direct = true;
     else if (s == "--direct-chain") a.direct_chain = std::atoi(next().c_str());
+    else if (s == "--nee") a.nee = true;
+    else if (s == "--nee-mis") {
+      const std::string v = next();
+      a.nee_mis = v == "0" ? 0 : v == "1" ? 1 : -1;
+    }
     else if (s == "--partition") {
       const std::string v = next();
       if (v == "tiles") a.partition = RT_PARTITION_TILES;
@@ -593,6 +619,13 @@ int main(int argc, char** argv) {
   if (a.gpus < 1 || a.gpus > 64) usage("--gpus must be in [1, 64]");
   if (a.progressive < 1) usage("--progressive must be >= 1");
   if (a.gpus > 1 && (a.progressive > 1 || !a.resume.empty())) usage("--progressive / --resume render on one GPU");
+
+  if (a.nee && (a.gpus > 1 || a.progressive > 1 || !a.resume.empty()))
+    usage("--nee renders on one GPU, without --progressive / --resume");
+  if (a.nee && (a.adaptive || a.denoise >= 0 || a.ao > 0.0 || a.direct))
+    usage("--nee replaces the colour render: no --adaptive, no --denoise, no --ao, no --direct");
+  if (a.nee && !a.dump_accum.empty()) usage("--nee frames are not checkpointed (--dump-accum)");
+  if (a.nee_mis != 0 && a.nee_mis != 1) usage("--nee-mis 0 or 1");
 
   if (a.adaptive && (a.gpus > 1 || a.progressive > 1 || !a.resume.empty()))
     usage("--adaptive renders on one GPU, without --progressive / --resume");

@@ -1,6 +1,6 @@
 // direct.h — the one-light-sample direct-lighting estimator of rt_render_direct (include/shirley_rt.h has its
-// definition, operation for operation), as a device function of its own so that a later path
-// integrator can call it at every Lambertian vertex unchanged.
+// definition, operation for operation), as a device function of its own so that the path
+// integrator (nee.hip) calls the same body at every Lambertian / FairyLight vertex.
 //
 // Only + - * /, sqrt_rn, comparisons and selects in the header's order (the build never fuses a*b+c), on the
 // path's own draws; the shadow ray goes through the any-hit walk occluded4 (occlusion.h).
@@ -16,11 +16,17 @@ constexpr double kShadowTMin = 0.001;
 constexpr double kShadowTMax = 1.0 - 0x1p-20;
 
 // The estimate at a vertex (x, n) with scatter attenuation a, n_lights >= 1.  Consumes the path's draws
-// D (the pick), then two (rect) or three per attempt (sphere).
-template <int THREADS, int MODE>
+// D (the pick), then two (rect) or three per attempt (sphere).  `taken` reports that the vertex took a light
+// sample (a cut or occluded one included): the path integrator (nee.hip) then weights the emission its scatter
+// lands on.  MIS: the sample carries the balance-heuristic weight against the Lambertian scatter, whose density
+// in area measure at the light is gs = ((cx * cy) / d2) / pi, the light sample's being pl = 1 / (area * L):
+// g = (1 / pl) * (pl / (pl + gs)) * gs = gs / (pl + gs) in place of gs / pl (rt_render_nee, shirley_rt.h).
+template <int THREADS, int MODE, bool MIS>
 __device__ __forceinline__ v3 direct_light(const DScene& S, const DNode4F* lds_nodes, const DPrim* lds_prims,
                                            const DLight* __restrict__ lights, int n_lights, Rng& rng, uint64_t seed,
-                                           v3 x, v3 n, v3 a, unsigned* stk, unsigned& visits, unsigned& ptests) {
+                                           v3 x, v3 n, v3 a, unsigned* stk, unsigned& visits, unsigned& ptests,
+                                           bool& taken) {
+  taken = true;
   const double nl = (double)n_lights;
   const int pick = (int)(rng_next(rng, seed) * nl);
   const DLight& L = lights[pick < n_lights - 1 ? pick : n_lights - 1];
@@ -54,8 +60,25 @@ __device__ __forceinline__ v3 direct_light(const DScene& S, const DNode4F* lds_n
     return V(0.0, 0.0, 0.0);
   v3 le = V(L.color[0], L.color[1], L.color[2]);
   if (L.emitter == RT_MAT_FAIRY_LIGHT) le = scale(le, cy);  // lighting.rs:59-65 for the ray (x, w)
-  const double g = ((cx * cy) / d2) * ((L.area * nl) / kDirectPi);
+  double g;
+  if (MIS) {
+    const double gs = ((cx * cy) / d2) / kDirectPi;
+    const double pl = 1.0 / (L.area * nl);
+    g = gs / (pl + gs);
+  } else {
+    g = ((cx * cy) / d2) * ((L.area * nl) / kDirectPi);
+  }
   return scale(hmul(a, le), g);
+}
+
+// The plain form (rt_render_direct's estimator).
+template <int THREADS, int MODE>
+__device__ __forceinline__ v3 direct_light(const DScene& S, const DNode4F* lds_nodes, const DPrim* lds_prims,
+                                           const DLight* __restrict__ lights, int n_lights, Rng& rng, uint64_t seed,
+                                           v3 x, v3 n, v3 a, unsigned* stk, unsigned& visits, unsigned& ptests) {
+  bool taken;
+  return direct_light<THREADS, MODE, false>(S, lds_nodes, lds_prims, lights, n_lights, rng, seed, x, n, a, stk, visits,
+                                            ptests, taken);
 }
 
 }  // namespace rt

@@ -504,7 +504,7 @@ int rt_destroy(rt_ctx* c) {
   if (!c) return RT_OK;
   (void)hipSetDevice(c->device);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
-  for (DevBuf* b : {&c->nodes, &c->nodes4, &c->prims, &c->mats, &c->texs, &c->perlin, &c->texels, &c->exts, &c->ground, &c->lights, &c->partial, &c->kcam, &c->shutter0, &c->moments, &c->tile_list, &c->tile_err, &c->dn_a, &c->dn_b, &c->feat,
+  for (DevBuf* b : {&c->nodes, &c->nodes4, &c->prims, &c->mats, &c->texs, &c->perlin, &c->texels, &c->exts, &c->ground, &c->lights, &c->prim_light, &c->partial, &c->kcam, &c->shutter0, &c->moments, &c->tile_list, &c->tile_err, &c->dn_a, &c->dn_b, &c->feat,
                     &c->accum, &c->counters, &c->unit_counter, &c->wf_pool, &c->wf_iters, &c->packed, &c->gathered,
                     &c->parts, &c->band, &c->digests})
     release(*b);
@@ -552,6 +552,7 @@ int rt_scene_upload(rt_ctx* c, const rt_scene_desc* d, int32_t builder) {
   } else {
     release(c->lights);
   }
+  if ((st = up(c->prim_light, cs.prim_light))) return st;
   if ((st = ensure(c, c->shutter0, 2 * sizeof(double)))) return st;
   HIP_TRY(c, hipMemset(c->shutter0.p, 0, 2 * sizeof(double)));
 

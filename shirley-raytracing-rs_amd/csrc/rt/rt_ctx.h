@@ -49,6 +49,7 @@ struct rt_ctx {
   // the scene's light list (rt_scene_lights): the public records, and their device copies (DLight) that
   // rt_render_direct hands to its kernel as an argument of its own
   DevBuf lights;
+  DevBuf prim_light;  // rt_render_nee: device primitive number -> light-list index or -1, its own argument too
   std::vector<rt_light> light_list;
   int32_t n_unlisted_lights = 0;
   rt_scene_stats stats{};

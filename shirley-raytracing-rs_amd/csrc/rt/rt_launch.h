@@ -1,7 +1,7 @@
 // rt_launch.h — the launch wrappers of the HIP files, as the host side of the C ABI calls them.
 //
 // Included by rt_api.cpp, rt_multi.cpp, rt_denoise.cpp and by the files that define the wrappers (trace.hip,
-// trace_split.hip, wavefront.hip, features.hip, denoise.hip, occlusion.hip, direct.hip), so a changed signature fails to compile where
+// trace_split.hip, wavefront.hip, features.hip, denoise.hip, occlusion.hip, direct.hip, nee.hip), so a changed signature fails to compile where
 // it is changed.
 #pragma once
 
@@ -53,6 +53,10 @@ hipError_t launch_ao(const DScene& S, bool wide, const DCamera& C, uint64_t seed
 // direct.hip
 hipError_t launch_direct(const DScene& S, bool wide, const DCamera& C, uint64_t seed, int s_begin, int s_end, int chain,
                          const DLight* lights, int n_lights, double* emission, double* direct, hipStream_t stream);
+// nee.hip
+hipError_t launch_nee(const DScene& S, bool wide, bool mis, const DCamera& C, uint64_t seed, int s_begin, int s_end,
+                      int max_depth, const DLight* lights, int n_lights, const int32_t* prim_light, double* accum,
+                      hipStream_t stream);
 // trace_split.hip
 bool split_supported_nt(int nt);
 hipError_t split_prepare(const DScene& S, int nt, int* blocks_per_cu);

@@ -891,6 +891,9 @@ int compile_scene(const rt_scene_desc* d, int32_t builder, const SceneTuning& tu
       if (nd.leaf >= 0) nd.leaf = rank[nd.leaf];
     rd.objects = ranked.data();
     d = &rd;
+    // (a listed light is no instance, so flat_scene left it at its index)
+    cs.prim_light.assign(std::max<size_t>(1, cs.prim_object.size()), -1);
+    for (size_t j = 0; j < cs.lights.lights.size(); ++j) cs.prim_light[rank[cs.lights.lights[j].object]] = (int32_t)j;
   }
   flatten(tree, cs.nodes);
   std::vector<DNode4F> nodes4;

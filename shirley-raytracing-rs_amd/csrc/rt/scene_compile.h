@@ -102,6 +102,8 @@ struct CompiledScene {
   // flattened rotated spheres (flat_object): object index -> RotateY's cos, sin, for rt_scene_hit's u, v
   std::vector<std::pair<int32_t, std::pair<double, double>>> uv_fixups;
   LightList lights;
+  // device primitive number -> index into the light list, or -1 (rt_render_nee: which light a path landed on)
+  std::vector<int32_t> prim_light;
   rt_scene_stats stats{};
   uint64_t digest = 0;
   int32_t n_perlin = 0;

@@ -26,6 +26,7 @@ RT_BVH_NODES_GLOBAL, RT_BVH_NODES_HALF_LDS, RT_BVH_NODES_LDS = 0x100, 0x200, 0x4
 RT_ENGINE_AUTO, RT_ENGINE_MEGAKERNEL, RT_ENGINE_WAVEFRONT, RT_ENGINE_SPLIT, RT_ENGINE_TIMING = 0, 1, 2, 3, 0x10
 RT_TRAVERSAL_BINARY, RT_TRAVERSAL_RENDER = 0, 1
 RT_PARTITION_AUTO, RT_PARTITION_TILES, RT_PARTITION_SAMPLES = 0, 1, 2
+RT_NEE_MIS = 1  # rt_render_nee flags
 
 _d3 = C.c_double * 3
 _d6 = C.c_double * 6
@@ -227,6 +228,11 @@ RT_SIGNATURES = {
                                    C.c_void_p, C.c_void_p]),
     "rt_render_direct_device": (C.c_int, [C.c_void_p, C.POINTER(rt_camera), C.POINTER(rt_render_params), C.c_int32,
                                           C.c_void_p, C.c_void_p, C.c_void_p]),
+    # added within ABI 11: the light-sampling path integrator
+    "rt_render_nee": (C.c_int, [C.c_void_p, C.POINTER(rt_camera), C.POINTER(rt_render_params), C.c_int32,
+                                C.c_void_p]),
+    "rt_render_nee_device": (C.c_int, [C.c_void_p, C.POINTER(rt_camera), C.POINTER(rt_render_params), C.c_int32,
+                                       C.c_void_p, C.c_void_p]),
 }
 
 # every symbol declared in include/shirley_host.h

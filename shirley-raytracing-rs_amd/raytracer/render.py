@@ -355,6 +355,23 @@ class Device:
             self._h, C.byref(camera), C.byref(p), int(chain), C.c_void_p(emission_ptr or None),
             C.c_void_p(direct_ptr or None), C.c_void_p(stream or None)))
 
+    def render_nee(self, camera: N.rt_camera, settings: RenderSettings, mis: bool = True) -> np.ndarray:
+        """rt_render_nee -> [H][W][3] f64 sums over the settings' sample range, row 0 = bottom (render's layout):
+        the path integrator with one light sample per Lambertian / FairyLight vertex; `mis` weights light sample
+        and scatter by the balance heuristic (RT_NEE_MIS), else the light sample takes the listed lights whole."""
+        out = np.zeros((camera.image_height, camera.image_width, 3), dtype=np.float64)
+        p = settings.params()
+        _check(self._h, N.rt_lib().rt_render_nee(self._h, C.byref(camera), C.byref(p), N.RT_NEE_MIS if mis else 0,
+                                                 out.ctypes.data))
+        return out
+
+    def render_nee_device(self, camera, settings: RenderSettings, mis: bool, accum_ptr: int, stream: int = 0):
+        """rt_render_nee_device: a device [H][W][3] f64 output; asynchronous on `stream`."""
+        p = settings.params()
+        _check(self._h, N.rt_lib().rt_render_nee_device(self._h, C.byref(camera), C.byref(p),
+                                                        N.RT_NEE_MIS if mis else 0, C.c_void_p(accum_ptr or None),
+                                                        C.c_void_p(stream or None)))
+
     def probe(self, rays: np.ndarray, seed: int, sample: int = 0, draw: int = 0):
         """One iteration of ray_color's loop (render.rs:30-46) per ray through the megakernel's device code
         (rt_probe_segment): ray i on the path key (seed, pixel = i, sample, draw) -> rt_probe array
