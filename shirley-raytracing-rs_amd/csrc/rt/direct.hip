@@ -1,21 +1,21 @@
 // direct.hip — rt_render_direct: per-pixel sums of the feature vertex's emission and of a one-light-sample
 // estimate of its direct illumination from the scene's light list (include/shirley_rt.h).
 //
-// direct_kernel is features_kernel's walk (features.hip: one wave per 8x8 tile, one lane per pixel, the sample
-// loop inside the lane, the same camera ray and dielectric chain, the wave's marble for a Perlin albedo, so
-// lanes of an edge tile outside the image stay, idle, for that wave-wide step) followed, at a Lambertian or
-// FairyLight vertex, by direct_light (direct.h), whose shadow ray asks occluded4 as ao_kernel does
-// (occlusion.hip).  The light table is a kernel argument of its own.  No atomics, no inter-wave traffic.
+// direct_kernel is a tile pass (one wave per 8x8 tile, one lane per pixel, the sample loop inside the lane, the
+// camera ray and the dielectric chain to the feature vertex, the wave's marble for a Perlin albedo, so lanes of
+// an edge tile outside the image stay, idle, for that wave-wide step) that, at a Lambertian or FairyLight vertex,
+// calls direct_light (direct.h), whose shadow ray asks the any-hit walk occluded4 (occlusion.h).  The light table
+// is a kernel argument of its own.  No atomics, no inter-wave traffic.  Its block size and launch are the frame's
+// (pass_frame.h); the kernel spells the frame's device pieces out, because with any of them it runs 0.5 % slower
+// on the night frame (profiles/passframe/direct_pieces.json).
 // Reference scenes only (no book-2 records): EXT = false instances.
 #include <hip/hip_runtime.h>
 
 #include "direct.h"
+#include "pass_frame.h"
 #include "rt_launch.h"
 
 namespace rt {
-
-// Block of the scene-in-LDS placements (`wide`), as features.hip's and occlusion.hip's.
-constexpr int kDirectThreadsWide = kTraceThreadsWide;
 
 template <int THREADS, int MODE>
 __global__ __launch_bounds__(THREADS) void direct_kernel(DScene S, DCamera C, uint64_t seed, int s_begin, int s_end,
@@ -70,7 +70,7 @@ __global__ __launch_bounds__(THREADS) void direct_kernel(DScene S, DCamera C, ui
       const double jy = (double)py + rng_next(rng, seed);
       camera_ray(C, rng, seed, jx, jy, o, d);
       int left = chain;
-      for (;;) {  // features_kernel's walk to the feature vertex
+      for (;;) {  // through at most `chain` dielectric vertices; each kernel keeps this loop
         double t_best = __builtin_inf();
         face = -1;
         prim = traverse4<THREADS, MODE, false>(S, lds_nodes, lds_prims, o, d, 0.001, t_best, face, stk, rng, seed,
@@ -136,41 +136,17 @@ __global__ __launch_bounds__(THREADS) void direct_kernel(DScene S, DCamera C, ui
   }
 }
 
-template <int THREADS, int MODE>
-static hipError_t launch_direct_1(const DScene& S, const DCamera& C, uint64_t seed, int s_begin, int s_end, int chain,
-                                  const DLight* lights, int n_lights, double* emission, double* direct,
-                                  hipStream_t stream) {
-  const int tiles_x = (C.width + kTile - 1) / kTile, tiles_y = (C.height + kTile - 1) / kTile;
-  const int n_tiles = tiles_x * tiles_y;
-  const int per_block = THREADS / kWave;
-  const int blocks = (n_tiles + per_block - 1) / per_block;
-  const size_t lds = trace_lds_bytes(S.n_lds_nodes4, node4_bytes(false), MODE == kSceneLds ? S.n_lds_prims : 0,
-                                     MODE == kSceneLds ? S.n_lds_perlin : 0, S.stack_depth4, THREADS,
-                                     MODE == kSceneLds ? S.n_lds_mats : 0, MODE == kSceneLds ? S.n_lds_texs : 0);
-  hipError_t e = hipFuncSetAttribute((const void*)direct_kernel<THREADS, MODE>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)lds);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((direct_kernel<THREADS, MODE>), dim3(blocks), dim3(THREADS), lds, stream, S, C, seed, s_begin, s_end,
-                     chain, tiles_x, n_tiles, lights, n_lights, emission, direct);
-  return hipGetLastError();
-}
-
-// rt_render_direct: block and placement chosen as launch_features does
+// rt_render_direct
 hipError_t launch_direct(const DScene& S, bool wide, const DCamera& C, uint64_t seed, int s_begin, int s_end, int chain,
                          const DLight* lights, int n_lights, double* emission, double* direct, hipStream_t stream) {
   if (S.exts) return hipErrorInvalidValue;  // (the caller refuses book-2 scenes)
   if (n_lights > 0 && !lights) return hipErrorInvalidValue;
-  if (wide) {
-    if (S.n_lds_prims > 0)
-      return launch_direct_1<kDirectThreadsWide, kSceneLds>(S, C, seed, s_begin, s_end, chain, lights, n_lights, emission, direct, stream);
-    return launch_direct_1<kDirectThreadsWide, kNodesLds>(S, C, seed, s_begin, s_end, chain, lights, n_lights, emission, direct, stream);
-  }
-  const int mode = S.n_lds_nodes4 >= S.n_nodes4 ? kNodesLds : (S.n_lds_nodes4 == 0 ? kNodesGlobal : kNodesMixed);
-  switch (mode) {
-    case kNodesLds: return launch_direct_1<kHitThreads, kNodesLds>(S, C, seed, s_begin, s_end, chain, lights, n_lights, emission, direct, stream);
-    case kNodesGlobal: return launch_direct_1<kHitThreads, kNodesGlobal>(S, C, seed, s_begin, s_end, chain, lights, n_lights, emission, direct, stream);
-    default: return launch_direct_1<kHitThreads, kNodesMixed>(S, C, seed, s_begin, s_end, chain, lights, n_lights, emission, direct, stream);
-  }
+  const TileGrid G = tile_grid(C);
+  return dispatch_placement<kPassThreadsWide>(S, wide, [&](auto threads, auto mode) {
+    constexpr int T = decltype(threads)::value, M = decltype(mode)::value;
+    return launch_block(direct_kernel<T, M>, G.blocks(T), T, block_lds_bytes<M>(S, node4_bytes(false), T), stream, S, C,
+                        seed, s_begin, s_end, chain, G.tiles_x, G.n_tiles, lights, n_lights, emission, direct);
+  });
 }
 
 }  // namespace rt

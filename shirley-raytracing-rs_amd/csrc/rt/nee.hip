@@ -1,8 +1,8 @@
 // nee.hip — rt_render_nee: a path integrator that takes one light sample at every Lambertian / FairyLight
 // vertex and weights the emission its scatter then lands on (include/shirley_rt.h).
 //
-// nee_kernel keeps direct_kernel's frame (direct.hip: one wave per 8x8 tile, one lane per pixel, the same LDS
-// layout and placements, EXT = false) and runs whole paths in it by lane-level path regeneration: one
+// nee_kernel stands in the tile-pass frame (pass_frame.h: one wave per 8x8 tile, one lane per pixel, the block's
+// LDS layout and placements, EXT = false) and runs whole paths in it by lane-level path regeneration: one
 // wave-uniform loop whose iteration traces one segment per live lane with probe_kernel's body (trace.hip:
 // traverse4, hit_record, the wave's marble_coop and draws_coop, shade_factor — the megakernel's device
 // functions on the megakernel's draws), then applies the weight ws to the segment's emission and calls
@@ -15,11 +15,10 @@
 #include <hip/hip_runtime.h>
 
 #include "direct.h"
+#include "pass_frame.h"
 #include "rt_launch.h"
 
 namespace rt {
-
-constexpr int kNeeThreadsWide = kTraceThreadsWide;
 
 template <int THREADS, int MODE, bool MIS>
 __global__ __launch_bounds__(THREADS) void nee_kernel(DScene S, DCamera C, uint64_t seed, int s_begin, int s_end,
@@ -28,29 +27,12 @@ __global__ __launch_bounds__(THREADS) void nee_kernel(DScene S, DCamera C, uint6
                                                       const int32_t* __restrict__ prim_light,
                                                       double* __restrict__ accum) {
   extern __shared__ unsigned char lds_raw[];
-  const int tid = threadIdx.x;
-  typedef DNode4F N4;
-  N4* lds_nodes = reinterpret_cast<N4*>(lds_raw);
-  DPrim* lds_prims = reinterpret_cast<DPrim*>(lds_raw + (size_t)S.n_lds_nodes4 * sizeof(N4));
-  const DPerlin* lds_perlin = (MODE == kSceneLds && S.n_lds_perlin > 0)
-                                  ? reinterpret_cast<const DPerlin*>(lds_prims + S.n_lds_prims)
-                                  : nullptr;
-  unsigned char* stk_base = lds_raw + (size_t)S.n_lds_nodes4 * sizeof(N4) +
-                            (MODE == kSceneLds ? (size_t)S.n_lds_prims * sizeof(DPrim) +
-                                                     (size_t)S.n_lds_perlin * sizeof(DPerlin) +
-                                                     (size_t)S.n_lds_mats * sizeof(DMat) +
-                                                     (size_t)S.n_lds_texs * sizeof(DTex)
-                                               : 0);
-  unsigned* stk = reinterpret_cast<unsigned*>(stk_base) + tid;
-  stage_nodes4<MODE>(S, lds_nodes, lds_prims);
-  // wave w of the block renders tile blockIdx * (THREADS / 64) + w; lane l its pixel (l % 8, l / 8)
-  const int tile = blockIdx.x * (THREADS / kWave) + tid / kWave;
-  const int lane = tid % kWave;
-  const int px = (tile % tiles_x) * kTile + lane % kTile;
-  const int py = (tile / tiles_x) * kTile + lane / kTile;
-  if (tile >= n_tiles) return;  // (a whole wave past the last tile leaves together)
-  const bool active = px < C.width && py < C.height;
-  const uint32_t pix = (uint32_t)py * (uint32_t)C.width + (uint32_t)px;
+  const BlockLds<DNode4F> L = carve_block_lds<MODE, DNode4F>(S, lds_raw);
+  stage_nodes4<MODE>(S, L.nodes, L.prims);
+  const TileLane T = tile_lane<THREADS>(tiles_x);
+  if (T.tile >= n_tiles) return;
+  const bool active = T.active(C);
+  const uint32_t pix = T.pix(C);
   unsigned visits = 0, ptests = 0;
 #ifdef RT_PHASE_TIMING
   unsigned long long steps = 0;
@@ -71,9 +53,7 @@ __global__ __launch_bounds__(THREADS) void nee_kernel(DScene S, DCamera C, uint6
     if (__ballot(live) == 0ull) break;  // wave-uniform: the wave's last lane is done
     if (live && fresh) {  // the next sample's camera ray (render.rs:60-63)
       rng = Rng{pix, (uint32_t)s, 0u, 0u, 0u};
-      const double jx = (double)px + rng_next(rng, seed);
-      const double jy = (double)py + rng_next(rng, seed);
-      camera_ray(C, rng, seed, jx, jy, o, d);
+      sample_ray(C, rng, seed, T.px, T.py, o, d);
       att = V(1.0, 1.0, 1.0);
       rad = V(0.0, 0.0, 0.0);
       k = 1;
@@ -90,30 +70,22 @@ __global__ __launch_bounds__(THREADS) void nee_kernel(DScene S, DCamera C, uint6
     h.t = h.u = h.v = 0.0;
     h.front_face = false;
     if (live) {
-      prim = traverse4<THREADS, MODE, false>(S, lds_nodes, lds_prims, o, d, 0.001, t_best, face, stk, rng, seed, visits,
+      prim = traverse4<THREADS, MODE, false>(S, L.nodes, L.prims, o, d, 0.001, t_best, face, L.stk, rng, seed, visits,
                                              ptests RT_STAT_ARG(steps));
       if (prim >= 0) {
         hit = true;
-        const DPrim pr = (MODE == kSceneLds) ? lds_prims[prim] : S.prims[prim];
+        const DPrim pr = (MODE == kSceneLds) ? L.prims[prim] : S.prims[prim];
         hit_record<false, false>(S, pr, face, o, d, t_best, rng, seed, h);
         mat = pr.material;
         mk = S.mats[mat].kind;
         need_r = mk == RT_MAT_LAMBERTIAN || mk == RT_MAT_METAL || mk == RT_MAT_FAIRY_LIGHT || mk == RT_MAT_ISOTROPIC;
-        if (mk == RT_MAT_LAMBERTIAN || mk == RT_MAT_FAIRY_LIGHT || mk == RT_MAT_DIFFUSE_LIGHT || mk == RT_MAT_ISOTROPIC) {
-          leaf = resolve_texture(S, S.mats[mat].tex, h.point);
-          const DTex& tx = S.texs[leaf];
-          if (tx.kind == RT_TEX_PERLIN) {
-            need_pn = true;
-            ptab = tx.table;
-            psc = tx.scale;
-          }
-        }
+        if (mk == RT_MAT_LAMBERTIAN || mk == RT_MAT_FAIRY_LIGHT || mk == RT_MAT_DIFFUSE_LIGHT || mk == RT_MAT_ISOTROPIC)
+          leaf = texture_leaf(S, S.mats[mat].tex, h.point, need_pn, ptab, psc);
       }
     }
     const bool ends = live && (!hit || mk == RT_MAT_DIFFUSE_LIGHT);
     // step 3: the wave's marble values and draws (every lane of the wave is here)
-    const double pn = lds_perlin ? marble_coop((LdsPerlin*)lds_perlin, need_pn, ptab, psc, h.point)
-                                 : marble_coop(S.perlin, need_pn, ptab, psc, h.point);
+    const double pn = wave_marble(S, L.perlin, need_pn, ptab, psc, h.point);
     const bool scat = live && !ends;
     const int dk = (scat && need_r) ? kDrawSphere : (scat && mk == RT_MAT_DIELECTRIC) ? kDrawDiel : kDrawNone;
     double jx0 = 0.0, jy0 = 0.0;
@@ -157,8 +129,8 @@ __global__ __launch_bounds__(THREADS) void nee_kernel(DScene S, DCamera C, uint6
           prev = false;
           if ((mk == RT_MAT_LAMBERTIAN || mk == RT_MAT_FAIRY_LIGHT) && n_lights > 0 && k < max_depth) {
             // on the path's draws after the scatter's own; stands for segment k + 1's emission
-            const v3 dl = direct_light<THREADS, MODE, MIS>(S, lds_nodes, lds_prims, lights, n_lights, rng, seed, h.point,
-                                                           h.normal, mul, stk, visits, ptests, prev);
+            const v3 dl = direct_light<THREADS, MODE, MIS>(S, L.nodes, L.prims, lights, n_lights, rng, seed, h.point,
+                                                           h.normal, mul, L.stk, visits, ptests, prev);
             rad = rad + hmul(att, dl);
             cx_prev = dot(h.normal, d) / sqrt_rn(len2(d));
           }
@@ -175,56 +147,27 @@ __global__ __launch_bounds__(THREADS) void nee_kernel(DScene S, DCamera C, uint6
     }
   }
   if (!active) return;
-  const size_t p = (size_t)py * (size_t)C.width + (size_t)px;
+  const size_t p = (size_t)T.py * (size_t)C.width + (size_t)T.px;
   accum[p * 3 + 0] = sum.x;
   accum[p * 3 + 1] = sum.y;
   accum[p * 3 + 2] = sum.z;
 }
 
-template <int THREADS, int MODE, bool MIS>
-static hipError_t launch_nee_1(const DScene& S, const DCamera& C, uint64_t seed, int s_begin, int s_end, int max_depth,
-                               const DLight* lights, int n_lights, const int32_t* prim_light, double* accum,
-                               hipStream_t stream) {
-  const int tiles_x = (C.width + kTile - 1) / kTile, tiles_y = (C.height + kTile - 1) / kTile;
-  const int n_tiles = tiles_x * tiles_y;
-  const int per_block = THREADS / kWave;
-  const int blocks = (n_tiles + per_block - 1) / per_block;
-  const size_t lds = trace_lds_bytes(S.n_lds_nodes4, node4_bytes(false), MODE == kSceneLds ? S.n_lds_prims : 0,
-                                     MODE == kSceneLds ? S.n_lds_perlin : 0, S.stack_depth4, THREADS,
-                                     MODE == kSceneLds ? S.n_lds_mats : 0, MODE == kSceneLds ? S.n_lds_texs : 0);
-  hipError_t e = hipFuncSetAttribute((const void*)nee_kernel<THREADS, MODE, MIS>,
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((nee_kernel<THREADS, MODE, MIS>), dim3(blocks), dim3(THREADS), lds, stream, S, C, seed, s_begin,
-                     s_end, max_depth, tiles_x, n_tiles, lights, n_lights, prim_light, accum);
-  return hipGetLastError();
-}
-
-template <bool MIS>
-static hipError_t launch_nee_m(const DScene& S, bool wide, const DCamera& C, uint64_t seed, int s_begin, int s_end,
-                               int max_depth, const DLight* lights, int n_lights, const int32_t* prim_light,
-                               double* accum, hipStream_t stream) {
-  if (wide) {
-    if (S.n_lds_prims > 0)
-      return launch_nee_1<kNeeThreadsWide, kSceneLds, MIS>(S, C, seed, s_begin, s_end, max_depth, lights, n_lights, prim_light, accum, stream);
-    return launch_nee_1<kNeeThreadsWide, kNodesLds, MIS>(S, C, seed, s_begin, s_end, max_depth, lights, n_lights, prim_light, accum, stream);
-  }
-  const int mode = S.n_lds_nodes4 >= S.n_nodes4 ? kNodesLds : (S.n_lds_nodes4 == 0 ? kNodesGlobal : kNodesMixed);
-  switch (mode) {
-    case kNodesLds: return launch_nee_1<kHitThreads, kNodesLds, MIS>(S, C, seed, s_begin, s_end, max_depth, lights, n_lights, prim_light, accum, stream);
-    case kNodesGlobal: return launch_nee_1<kHitThreads, kNodesGlobal, MIS>(S, C, seed, s_begin, s_end, max_depth, lights, n_lights, prim_light, accum, stream);
-    default: return launch_nee_1<kHitThreads, kNodesMixed, MIS>(S, C, seed, s_begin, s_end, max_depth, lights, n_lights, prim_light, accum, stream);
-  }
-}
-
-// rt_render_nee: block and placement chosen as launch_features does
+// rt_render_nee
 hipError_t launch_nee(const DScene& S, bool wide, bool mis, const DCamera& C, uint64_t seed, int s_begin, int s_end,
                       int max_depth, const DLight* lights, int n_lights, const int32_t* prim_light, double* accum,
                       hipStream_t stream) {
   if (S.exts) return hipErrorInvalidValue;  // (the caller refuses book-2 scenes)
   if (!accum || !prim_light || (n_lights > 0 && !lights)) return hipErrorInvalidValue;
-  return mis ? launch_nee_m<true>(S, wide, C, seed, s_begin, s_end, max_depth, lights, n_lights, prim_light, accum, stream)
-             : launch_nee_m<false>(S, wide, C, seed, s_begin, s_end, max_depth, lights, n_lights, prim_light, accum, stream);
+  const TileGrid G = tile_grid(C);
+  return dispatch_placement<kPassThreadsWide>(S, wide, [&](auto threads, auto mode) {
+    constexpr int T = decltype(threads)::value, M = decltype(mode)::value;
+    auto go = [&](auto kernel) {
+      return launch_block(kernel, G.blocks(T), T, block_lds_bytes<M>(S, node4_bytes(false), T), stream, S, C, seed,
+                          s_begin, s_end, max_depth, G.tiles_x, G.n_tiles, lights, n_lights, prim_light, accum);
+    };
+    return mis ? go(nee_kernel<T, M, true>) : go(nee_kernel<T, M, false>);
+  });
 }
 
 }  // namespace rt

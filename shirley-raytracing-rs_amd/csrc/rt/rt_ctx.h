@@ -162,4 +162,65 @@ int resolve_range(rt_ctx* c, const rt_render_params* p, SampleRange* r);
 int render_window(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, const SampleRange& R, int ty0, int ty1,
                   int row0, int row1, int packed, double* out_dev, hipStream_t s, const TileStep* step = nullptr);
 
+// The device forms of the tile passes (rt_render_{features,ao,direct,nee}_device) open with pass_check and, after
+// their own argument checks, go on with pass_begin (pass_range, then pass_device), so every entry point keeps the
+// order in which its refusals win; `name` is the entry point's, for the messages.
+inline int check_single_rank(rt_ctx* c, const rt_render_params* p, const char* name) {
+  return p->tile_world != 1 ? fail(c, RT_E_INVALID, "%s: tile_world must be 1", name) : RT_OK;
+}
+inline int pass_check(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, const char* name) {
+  const int st = check_render_args(c, cam, p);
+  return st ? st : check_single_rank(c, p, name);
+}
+inline int pass_range(rt_ctx* c, const rt_render_params* p, const char* name, SampleRange* R) {
+  if (resolve_range(c, p, R)) return RT_E_INVALID;
+  if (c->scene.exts) return fail(c, RT_E_UNSUPPORTED, "%s: scenes with book-2 objects are not supported", name);
+  return RT_OK;
+}
+inline int pass_device(rt_ctx* c, void* stream, hipStream_t* s) {
+  resolve_stream(c, stream, s);
+  HIP_TRY(c, hipSetDevice(c->device));
+  return RT_OK;
+}
+inline int pass_begin(rt_ctx* c, const rt_render_params* p, void* stream, const char* name, SampleRange* R,
+                      hipStream_t* s) {
+  const int st = pass_range(c, p, name, R);
+  return st ? st : pass_device(c, stream, s);
+}
+
+// Their host-buffer forms: check_host_pass, the pass's own checks, then pass_to_host, which lays the planes out
+// in c->feat (a plane without a host buffer keeps its place and gets a null device pointer), runs the device
+// form on c->stream, copies the wanted planes back and synchronises.
+inline int check_host_pass(rt_ctx* c, const rt_camera* cam) {
+  if (!c) return RT_E_INVALID;
+  if (!cam) return fail(c, RT_E_INVALID, "camera/params is NULL");
+  if (cam->image_width < 1 || cam->image_height < 1) return fail(c, RT_E_INVALID, "bad image size");
+  return RT_OK;
+}
+struct HostPlane {
+  double* host;
+  size_t count;  // doubles
+  double* dev = nullptr;
+};
+template <class F>
+int pass_to_host(rt_ctx* c, HostPlane* planes, int n, F device_form) {
+  size_t total = 0;
+  for (int i = 0; i < n; ++i) total += planes[i].count;
+  int st = ensure(c, c->feat, total * sizeof(double));
+  if (st) return st;
+  double* at = static_cast<double*>(c->feat.p);
+  for (int i = 0; i < n; ++i) {
+    planes[i].dev = planes[i].host ? at : nullptr;
+    at += planes[i].count;
+  }
+  st = device_form();
+  if (st) return st;
+  for (int i = 0; i < n; ++i)
+    if (planes[i].host)
+      HIP_TRY(c, hipMemcpyAsync(planes[i].host, planes[i].dev, planes[i].count * sizeof(double), hipMemcpyDeviceToHost,
+                                c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return RT_OK;
+}
+
 }  // namespace rt

@@ -9,18 +9,14 @@ extern "C" {
 
 int rt_render_features_device(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, int32_t chain,
                               double* albedo_dev, double* normal_dev, double* depth_dev, void* stream) {
-  int st = check_render_args(c, cam, p);
+  int st = pass_check(c, cam, p, "rt_render_features");
   if (st) return st;
-  if (p->tile_world != 1) return fail(c, RT_E_INVALID, "rt_render_features: tile_world must be 1");
   if (chain < 0) return fail(c, RT_E_INVALID, "rt_render_features: negative chain");
   SampleRange R;
-  if (resolve_range(c, p, &R)) return RT_E_INVALID;
-  if (c->scene.exts)
-    return fail(c, RT_E_UNSUPPORTED, "rt_render_features: scenes with book-2 objects are not supported");
-  if (!albedo_dev && !normal_dev && !depth_dev) return RT_OK;
   hipStream_t s;
-  resolve_stream(c, stream, &s);
-  HIP_TRY(c, hipSetDevice(c->device));
+  if ((st = pass_range(c, p, "rt_render_features", &R))) return st;
+  if (!albedo_dev && !normal_dev && !depth_dev) return RT_OK;  // (before the device is touched)
+  if ((st = pass_device(c, stream, &s))) return st;
   HIP_TRY(c, launch_features(c->scene, c->place.wide, device_camera(cam), p->seed, R.begin, R.end, chain, albedo_dev,
                              normal_dev, depth_dev, s));
   return RT_OK;
@@ -28,23 +24,13 @@ int rt_render_features_device(rt_ctx* c, const rt_camera* cam, const rt_render_p
 
 int rt_render_features(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, int32_t chain, double* albedo_host,
                        double* normal_host, double* depth_host) {
-  if (!c) return RT_E_INVALID;
-  if (!cam) return fail(c, RT_E_INVALID, "camera/params is NULL");
-  if (cam->image_width < 1 || cam->image_height < 1) return fail(c, RT_E_INVALID, "bad image size");
+  const int st = check_host_pass(c, cam);
+  if (st) return st;
   const size_t n_px = (size_t)cam->image_width * cam->image_height;
-  int st = ensure(c, c->feat, n_px * 7 * sizeof(double));
-  if (st) return st;
-  double* base = static_cast<double*>(c->feat.p);
-  double* a = albedo_host ? base : nullptr;
-  double* n = normal_host ? base + n_px * 3 : nullptr;
-  double* z = depth_host ? base + n_px * 6 : nullptr;
-  st = rt_render_features_device(c, cam, p, chain, a, n, z, c->stream);
-  if (st) return st;
-  if (a) HIP_TRY(c, hipMemcpyAsync(albedo_host, a, n_px * 3 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  if (n) HIP_TRY(c, hipMemcpyAsync(normal_host, n, n_px * 3 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  if (z) HIP_TRY(c, hipMemcpyAsync(depth_host, z, n_px * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return RT_OK;
+  HostPlane pl[3] = {{albedo_host, n_px * 3}, {normal_host, n_px * 3}, {depth_host, n_px}};
+  return pass_to_host(c, pl, 3, [&] {
+    return rt_render_features_device(c, cam, p, chain, pl[0].dev, pl[1].dev, pl[2].dev, c->stream);
+  });
 }
 
 int rt_denoise(const rt_denoise_inputs* in, const rt_denoise_params* prm, double* out) {

@@ -33,18 +33,13 @@ int rt_scene_lights_host(const rt_scene_desc* d, int32_t* n_lights, int32_t* n_u
 
 int rt_render_direct_device(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, int32_t chain,
                             double* emission_dev, double* direct_dev, void* stream) {
-  int st = check_render_args(c, cam, p);
+  int st = pass_check(c, cam, p, "rt_render_direct");
   if (st) return st;
-  if (p->tile_world != 1) return fail(c, RT_E_INVALID, "rt_render_direct: tile_world must be 1");
   if (chain < 0) return fail(c, RT_E_INVALID, "rt_render_direct: negative chain");
   if (!emission_dev && !direct_dev) return fail(c, RT_E_INVALID, "rt_render_direct: both output buffers are NULL");
   SampleRange R;
-  if (resolve_range(c, p, &R)) return RT_E_INVALID;
-  if (c->scene.exts)
-    return fail(c, RT_E_UNSUPPORTED, "rt_render_direct: scenes with book-2 objects are not supported");
   hipStream_t s;
-  resolve_stream(c, stream, &s);
-  HIP_TRY(c, hipSetDevice(c->device));
+  if ((st = pass_begin(c, p, stream, "rt_render_direct", &R, &s))) return st;
   const int n_lights = (int)c->light_list.size();
   HIP_TRY(c, launch_direct(c->scene, c->place.wide, device_camera(cam), p->seed, R.begin, R.end, chain,
                            n_lights ? static_cast<const DLight*>(c->lights.p) : nullptr, n_lights, emission_dev,
@@ -54,21 +49,14 @@ int rt_render_direct_device(rt_ctx* c, const rt_camera* cam, const rt_render_par
 
 int rt_render_direct(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, int32_t chain, double* emission_host,
                      double* direct_host) {
-  if (!c) return RT_E_INVALID;
-  if (!cam) return fail(c, RT_E_INVALID, "camera/params is NULL");
-  if (cam->image_width < 1 || cam->image_height < 1) return fail(c, RT_E_INVALID, "bad image size");
+  const int st = check_host_pass(c, cam);
+  if (st) return st;
   if (!emission_host && !direct_host) return fail(c, RT_E_INVALID, "rt_render_direct: both output buffers are NULL");
   const size_t n = (size_t)cam->image_width * cam->image_height * 3;
-  int st = ensure(c, c->feat, 2 * n * sizeof(double));
-  if (st) return st;
-  double* em = static_cast<double*>(c->feat.p);
-  double* di = em + n;
-  st = rt_render_direct_device(c, cam, p, chain, emission_host ? em : nullptr, direct_host ? di : nullptr, c->stream);
-  if (st) return st;
-  if (emission_host) HIP_TRY(c, hipMemcpyAsync(emission_host, em, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  if (direct_host) HIP_TRY(c, hipMemcpyAsync(direct_host, di, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return RT_OK;
+  HostPlane pl[2] = {{emission_host, n}, {direct_host, n}};
+  return pass_to_host(c, pl, 2, [&] {
+    return rt_render_direct_device(c, cam, p, chain, pl[0].dev, pl[1].dev, c->stream);
+  });
 }
 
 }  // extern "C"

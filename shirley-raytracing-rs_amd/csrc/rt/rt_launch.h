@@ -1,8 +1,10 @@
 // rt_launch.h — the launch wrappers of the HIP files, as the host side of the C ABI calls them.
 //
 // Included by rt_api.cpp, rt_multi.cpp, rt_denoise.cpp and by the files that define the wrappers (trace.hip,
-// trace_split.hip, wavefront.hip, features.hip, denoise.hip, occlusion.hip, direct.hip, nee.hip), so a changed signature fails to compile where
-// it is changed.
+// trace_split.hip, wavefront.hip, features.hip, denoise.hip, occlusion.hip, direct.hip, nee.hip), so a changed
+// signature fails to compile where it is changed.  The wrappers of the tile passes and of the ray batches
+// (launch_features, _occluded, _ao, _direct, _nee, _hit4, _probe) keep their own argument checks and place and
+// launch their kernel through pass_frame.h (dispatch_placement, block_lds_bytes, launch_block).
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -149,8 +149,8 @@ struct DPerlin {
 // wrappers (trace.hip, wavefront.hip) share.
 // megakernel block LDS: [n_lds_nodes4 x node4_bytes][n_lds_prims x DPrim][n_lds_perlin x DPerlin]
 // [n_lds_mats x DMat][n_lds_texs x DTex][stack_depth4 x threads packed entries]
-inline size_t trace_lds_bytes(int n_lds_nodes4, int node4_size, int n_lds_prims, int n_lds_perlin, int stack_depth4,
-                              int threads, int n_lds_mats, int n_lds_texs) {
+inline constexpr size_t trace_lds_bytes(int n_lds_nodes4, int node4_size, int n_lds_prims, int n_lds_perlin,
+                                        int stack_depth4, int threads, int n_lds_mats, int n_lds_texs) {
   return (size_t)n_lds_nodes4 * node4_size + (size_t)n_lds_prims * sizeof(DPrim) +
          (size_t)n_lds_perlin * sizeof(DPerlin) + (size_t)n_lds_mats * sizeof(DMat) + (size_t)n_lds_texs * sizeof(DTex) +
          (size_t)stack_depth4 * threads * kStack4EntryBytes;

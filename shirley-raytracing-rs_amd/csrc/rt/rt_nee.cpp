@@ -11,14 +11,11 @@ int rt_render_nee_device(rt_ctx* c, const rt_camera* cam, const rt_render_params
   int st = check_render_args(c, cam, p);
   if (st) return st;
   if (flags & ~(int32_t)RT_NEE_MIS) return fail(c, RT_E_INVALID, "rt_render_nee: unknown flag bits 0x%x", flags);
-  if (p->tile_world != 1) return fail(c, RT_E_INVALID, "rt_render_nee: tile_world must be 1");
+  if ((st = check_single_rank(c, p, "rt_render_nee"))) return st;  // (the flags are refused first: no pass_check)
   if (!accum_dev) return fail(c, RT_E_INVALID, "rt_render_nee: the output buffer is NULL");
   SampleRange R;
-  if (resolve_range(c, p, &R)) return RT_E_INVALID;
-  if (c->scene.exts) return fail(c, RT_E_UNSUPPORTED, "rt_render_nee: scenes with book-2 objects are not supported");
   hipStream_t s;
-  resolve_stream(c, stream, &s);
-  HIP_TRY(c, hipSetDevice(c->device));
+  if ((st = pass_begin(c, p, stream, "rt_render_nee", &R, &s))) return st;
   if (p->max_depth <= 0 || R.end <= R.begin) {  // no segment: zero sums
     const size_t n = (size_t)cam->image_width * cam->image_height * 3;
     HIP_TRY(c, hipMemsetAsync(accum_dev, 0, n * sizeof(double), s));
@@ -32,19 +29,11 @@ int rt_render_nee_device(rt_ctx* c, const rt_camera* cam, const rt_render_params
 }
 
 int rt_render_nee(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, int32_t flags, double* accum_host) {
-  if (!c) return RT_E_INVALID;
-  if (!cam) return fail(c, RT_E_INVALID, "camera/params is NULL");
-  if (cam->image_width < 1 || cam->image_height < 1) return fail(c, RT_E_INVALID, "bad image size");
+  const int st = check_host_pass(c, cam);
+  if (st) return st;
   if (!accum_host) return fail(c, RT_E_INVALID, "rt_render_nee: the output buffer is NULL");
-  const size_t n = (size_t)cam->image_width * cam->image_height * 3;
-  int st = ensure(c, c->feat, n * sizeof(double));
-  if (st) return st;
-  double* acc = static_cast<double*>(c->feat.p);
-  st = rt_render_nee_device(c, cam, p, flags, acc, c->stream);
-  if (st) return st;
-  HIP_TRY(c, hipMemcpyAsync(accum_host, acc, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return RT_OK;
+  HostPlane pl{accum_host, (size_t)cam->image_width * cam->image_height * 3};
+  return pass_to_host(c, &pl, 1, [&] { return rt_render_nee_device(c, cam, p, flags, pl.dev, c->stream); });
 }
 
 }  // extern "C"

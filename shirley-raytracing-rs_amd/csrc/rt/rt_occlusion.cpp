@@ -71,37 +71,25 @@ int rt_scene_occluded(rt_ctx* c, const double* rays, int32_t n, double t_min, do
 
 int rt_render_ao_device(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, int32_t chain, double radius,
                         double* ao_dev, void* stream) {
-  int st = check_render_args(c, cam, p);
+  int st = pass_check(c, cam, p, "rt_render_ao");
   if (st) return st;
-  if (p->tile_world != 1) return fail(c, RT_E_INVALID, "rt_render_ao: tile_world must be 1");
   if (chain < 0) return fail(c, RT_E_INVALID, "rt_render_ao: negative chain");
   if (!(radius > 0.0)) return fail(c, RT_E_INVALID, "rt_render_ao: radius must be > 0 (or +inf)");
   if (!ao_dev) return fail(c, RT_E_INVALID, "rt_render_ao: the output buffer is NULL");
   SampleRange R;
-  if (resolve_range(c, p, &R)) return RT_E_INVALID;
-  if (c->scene.exts) return fail(c, RT_E_UNSUPPORTED, "rt_render_ao: scenes with book-2 objects are not supported");
   hipStream_t s;
-  resolve_stream(c, stream, &s);
-  HIP_TRY(c, hipSetDevice(c->device));
+  if ((st = pass_begin(c, p, stream, "rt_render_ao", &R, &s))) return st;
   HIP_TRY(c, launch_ao(c->scene, c->place.wide, device_camera(cam), p->seed, R.begin, R.end, chain, radius, ao_dev, s));
   return RT_OK;
 }
 
 int rt_render_ao(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, int32_t chain, double radius,
                  double* ao_host) {
-  if (!c) return RT_E_INVALID;
-  if (!cam) return fail(c, RT_E_INVALID, "camera/params is NULL");
-  if (cam->image_width < 1 || cam->image_height < 1) return fail(c, RT_E_INVALID, "bad image size");
+  const int st = check_host_pass(c, cam);
+  if (st) return st;
   if (!ao_host) return fail(c, RT_E_INVALID, "rt_render_ao: the output buffer is NULL");
-  const size_t n_px = (size_t)cam->image_width * cam->image_height;
-  int st = ensure(c, c->feat, n_px * sizeof(double));
-  if (st) return st;
-  double* ao = static_cast<double*>(c->feat.p);
-  st = rt_render_ao_device(c, cam, p, chain, radius, ao, c->stream);
-  if (st) return st;
-  HIP_TRY(c, hipMemcpyAsync(ao_host, ao, n_px * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return RT_OK;
+  HostPlane pl{ao_host, (size_t)cam->image_width * cam->image_height};
+  return pass_to_host(c, &pl, 1, [&] { return rt_render_ao_device(c, cam, p, chain, radius, pl.dev, c->stream); });
 }
 
 }  // extern "C"

@@ -19,6 +19,7 @@
 //   * per-unit partial sums go to HBM once; a reduce kernel sums chunks in order (deterministic).
 #include "adaptive.h"
 #include "rt_device.h"
+#include "pass_frame.h"
 #include "rt_launch.h"
 
 #include <algorithm>
@@ -776,16 +777,8 @@ __global__ __launch_bounds__(kHitThreads) void hit4_kernel(DScene S, const doubl
   extern __shared__ unsigned char lds_raw[];
   const int tid = threadIdx.x;
   typedef typename Node4Sel<EXT>::T N4;
-  N4* lds_nodes = reinterpret_cast<N4*>(lds_raw);
-  DPrim* lds_prims = reinterpret_cast<DPrim*>(lds_raw + (size_t)S.n_lds_nodes4 * sizeof(N4));
-  unsigned char* stk_base = lds_raw + (size_t)S.n_lds_nodes4 * sizeof(N4) +
-                            (MODE == kSceneLds ? (size_t)S.n_lds_prims * sizeof(DPrim) +
-                                                     (size_t)S.n_lds_perlin * sizeof(DPerlin) +
-                                                     (size_t)S.n_lds_mats * sizeof(DMat) +
-                                                     (size_t)S.n_lds_texs * sizeof(DTex)
-                                               : 0);
-  unsigned* stk = reinterpret_cast<unsigned*>(stk_base) + tid;
-  stage_nodes4<MODE>(S, lds_nodes, lds_prims);
+  const BlockLds<N4> L = carve_block_lds<MODE, N4>(S, lds_raw);
+  stage_nodes4<MODE>(S, L.nodes, L.prims);
   const int i = blockIdx.x * kHitThreads + tid;
   if (i >= n) return;
   const v3 o = V(rays[i * 6 + 0], rays[i * 6 + 1], rays[i * 6 + 2]);
@@ -797,7 +790,7 @@ __global__ __launch_bounds__(kHitThreads) void hit4_kernel(DScene S, const doubl
 #ifdef RT_PHASE_TIMING
   unsigned long long steps = 0;
 #endif
-  const int prim = traverse4<kHitThreads, MODE, EXT>(S, lds_nodes, lds_prims, o, d, t_min, t_best, face, stk, rk, 0ull,
+  const int prim = traverse4<kHitThreads, MODE, EXT>(S, L.nodes, L.prims, o, d, t_min, t_best, face, L.stk, rk, 0ull,
                                                       visits, ptests RT_STAT_ARG(steps));
   HitOut r{};
   r.object = prim;
@@ -834,19 +827,8 @@ __global__ __launch_bounds__(kHitThreads) void probe_kernel(DScene S, const doub
   extern __shared__ unsigned char lds_raw[];
   const int tid = threadIdx.x;
   typedef typename Node4Sel<EXT>::T N4;
-  N4* lds_nodes = reinterpret_cast<N4*>(lds_raw);
-  DPrim* lds_prims = reinterpret_cast<DPrim*>(lds_raw + (size_t)S.n_lds_nodes4 * sizeof(N4));
-  const DPerlin* lds_perlin = (MODE == kSceneLds && S.n_lds_perlin > 0)
-                                  ? reinterpret_cast<const DPerlin*>(lds_prims + S.n_lds_prims)
-                                  : nullptr;
-  unsigned char* stk_base = lds_raw + (size_t)S.n_lds_nodes4 * sizeof(N4) +
-                            (MODE == kSceneLds ? (size_t)S.n_lds_prims * sizeof(DPrim) +
-                                                     (size_t)S.n_lds_perlin * sizeof(DPerlin) +
-                                                     (size_t)S.n_lds_mats * sizeof(DMat) +
-                                                     (size_t)S.n_lds_texs * sizeof(DTex)
-                                               : 0);
-  unsigned* stk = reinterpret_cast<unsigned*>(stk_base) + tid;
-  stage_nodes4<MODE>(S, lds_nodes, lds_prims);
+  const BlockLds<N4> L = carve_block_lds<MODE, N4>(S, lds_raw);
+  stage_nodes4<MODE>(S, L.nodes, L.prims);
   const int i = blockIdx.x * kHitThreads + tid;
   const bool active = i < n;
   v3 o = V(0.0, 0.0, 0.0), d = V(1.0, 1.0, 1.0);
@@ -875,30 +857,22 @@ __global__ __launch_bounds__(kHitThreads) void probe_kernel(DScene S, const doub
   h.t = h.u = h.v = 0.0;
   h.front_face = false;
   if (active) {
-    prim = traverse4<kHitThreads, MODE, EXT>(S, lds_nodes, lds_prims, o, d, 0.001, t_best, face, stk, rng, seed, visits,
+    prim = traverse4<kHitThreads, MODE, EXT>(S, L.nodes, L.prims, o, d, 0.001, t_best, face, L.stk, rng, seed, visits,
                                               ptests RT_STAT_ARG(steps));
     if (prim >= 0) {
       hit = true;
-      const DPrim pr = (MODE == kSceneLds) ? lds_prims[prim] : S.prims[prim];
+      const DPrim pr = (MODE == kSceneLds) ? L.prims[prim] : S.prims[prim];
       hit_record<false, EXT>(S, pr, face, o, d, t_best, rng, seed, h);
       mat = pr.material;
       mk = S.mats[mat].kind;
       need_r = mk == RT_MAT_LAMBERTIAN || mk == RT_MAT_METAL || mk == RT_MAT_FAIRY_LIGHT || mk == RT_MAT_ISOTROPIC;
-      if (mk == RT_MAT_LAMBERTIAN || mk == RT_MAT_FAIRY_LIGHT || mk == RT_MAT_DIFFUSE_LIGHT || mk == RT_MAT_ISOTROPIC) {
-        leaf = resolve_texture(S, S.mats[mat].tex, h.point);
-        const DTex& tx = S.texs[leaf];
-        if (tx.kind == RT_TEX_PERLIN) {
-          need_pn = true;
-          ptab = tx.table;
-          psc = tx.scale;
-        }
-      }
+      if (mk == RT_MAT_LAMBERTIAN || mk == RT_MAT_FAIRY_LIGHT || mk == RT_MAT_DIFFUSE_LIGHT || mk == RT_MAT_ISOTROPIC)
+        leaf = texture_leaf(S, S.mats[mat].tex, h.point, need_pn, ptab, psc);
     }
   }
   const bool ends = active && (!hit || mk == RT_MAT_DIFFUSE_LIGHT);
   // step 3: the wave's marble values and draws
-  const double pn = lds_perlin ? marble_coop((LdsPerlin*)lds_perlin, need_pn, ptab, psc, h.point)
-                               : marble_coop(S.perlin, need_pn, ptab, psc, h.point);
+  const double pn = wave_marble(S, L.perlin, need_pn, ptab, psc, h.point);
   const bool scat = active && !ends;
   const int dk = (scat && need_r) ? kDrawSphere : (scat && mk == RT_MAT_DIELECTRIC) ? kDrawDiel : kDrawNone;
   double jx = 0.0, jy = 0.0;
@@ -941,9 +915,6 @@ size_t hit_lds_bytes(int n_lds_nodes, int stack_depth) { return lds_bytes(n_lds_
 
 static int node_mode(const DScene& S) {
   return S.n_lds_nodes >= S.n_nodes ? kNodesLds : (S.n_lds_nodes == 0 ? kNodesGlobal : kNodesMixed);
-}
-static int node_mode4(const DScene& S) {
-  return S.n_lds_nodes4 >= S.n_nodes4 ? kNodesLds : (S.n_lds_nodes4 == 0 ? kNodesGlobal : kNodesMixed);
 }
 
 template <int THREADS, int MODE, bool EXT, int HOP = 0>
@@ -1061,78 +1032,37 @@ hipError_t launch_hit(const DScene& S, const double* rays, int n, double t_min, 
   return hipGetLastError();
 }
 
-template <int MODE, bool EXT>
-static hipError_t launch_hit4_1(const DScene& S, const double* rays, int n, double t_min, double t_max, HitOut* o,
-                                int blocks, hipStream_t stream) {
-  const size_t lds = trace_lds_bytes(S.n_lds_nodes4, node4_bytes(EXT), MODE == kSceneLds ? S.n_lds_prims : 0,
-                                     MODE == kSceneLds ? S.n_lds_perlin : 0, S.stack_depth4, kHitThreads,
-                                     MODE == kSceneLds ? S.n_lds_mats : 0, MODE == kSceneLds ? S.n_lds_texs : 0);
-  hipError_t e = hipFuncSetAttribute((const void*)hit4_kernel<MODE, EXT>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)lds);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((hit4_kernel<MODE, EXT>), dim3(blocks), dim3(kHitThreads), lds, stream, S, rays, n, t_min, t_max, o);
-  return hipGetLastError();
-}
-template <int MODE>
-static hipError_t launch_hit4_m(const DScene& S, const double* rays, int n, double t_min, double t_max, HitOut* o,
-                                int blocks, hipStream_t stream) {
-  return S.exts ? launch_hit4_1<MODE, true>(S, rays, n, t_min, t_max, o, blocks, stream)
-                : launch_hit4_1<MODE, false>(S, rays, n, t_min, t_max, o, blocks, stream);
-}
-
-// rt_scene_hit_ex(RT_TRAVERSAL_RENDER): the node / primitive placement the trace kernel uses
-// (`wide`: the scene-in-LDS block of launch_trace).
+// rt_scene_hit_ex(RT_TRAVERSAL_RENDER): the node / primitive placement the trace kernel uses (pass_frame.h
+// dispatch_placement; the block is kHitThreads on every placement) and the trace kernel's EXT instance.
 hipError_t launch_hit4(const DScene& S, bool wide, const double* rays, int n, double t_min, double t_max, void* out,
                        hipStream_t stream) {
   const int blocks = (n + kHitThreads - 1) / kHitThreads;
   if (blocks == 0) return hipSuccess;
   HitOut* o = static_cast<HitOut*>(out);
-  if (wide) {
-    if (S.n_lds_prims > 0) return launch_hit4_m<kSceneLds>(S, rays, n, t_min, t_max, o, blocks, stream);
-    return launch_hit4_m<kNodesLds>(S, rays, n, t_min, t_max, o, blocks, stream);
-  }
-  switch (node_mode4(S)) {
-    case kNodesLds: return launch_hit4_m<kNodesLds>(S, rays, n, t_min, t_max, o, blocks, stream);
-    case kNodesGlobal: return launch_hit4_m<kNodesGlobal>(S, rays, n, t_min, t_max, o, blocks, stream);
-    default: return launch_hit4_m<kNodesMixed>(S, rays, n, t_min, t_max, o, blocks, stream);
-  }
+  return dispatch_placement<kHitThreads>(S, wide, [&](auto, auto mode) {
+    constexpr int M = decltype(mode)::value;
+    auto go = [&](auto kernel, bool ext) {
+      return launch_block(kernel, blocks, kHitThreads, block_lds_bytes<M>(S, node4_bytes(ext), kHitThreads), stream, S,
+                          rays, n, t_min, t_max, o);
+    };
+    return S.exts ? go(hit4_kernel<M, true>, true) : go(hit4_kernel<M, false>, false);
+  });
 }
 
-template <int MODE, bool EXT>
-static hipError_t launch_probe_1(const DScene& S, const double* rays, int n, uint64_t seed, uint32_t sample,
-                                 uint32_t draw, ProbeOut* o, int blocks, hipStream_t stream) {
-  const size_t lds = trace_lds_bytes(S.n_lds_nodes4, node4_bytes(EXT), MODE == kSceneLds ? S.n_lds_prims : 0,
-                                     MODE == kSceneLds ? S.n_lds_perlin : 0, S.stack_depth4, kHitThreads,
-                                     MODE == kSceneLds ? S.n_lds_mats : 0, MODE == kSceneLds ? S.n_lds_texs : 0);
-  hipError_t e = hipFuncSetAttribute((const void*)probe_kernel<MODE, EXT>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)lds);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((probe_kernel<MODE, EXT>), dim3(blocks), dim3(kHitThreads), lds, stream, S, rays, n, seed, sample,
-                     draw, o);
-  return hipGetLastError();
-}
-template <int MODE>
-static hipError_t launch_probe_m(const DScene& S, const double* rays, int n, uint64_t seed, uint32_t sample,
-                                 uint32_t draw, ProbeOut* o, int blocks, hipStream_t stream) {
-  return S.exts ? launch_probe_1<MODE, true>(S, rays, n, seed, sample, draw, o, blocks, stream)
-                : launch_probe_1<MODE, false>(S, rays, n, seed, sample, draw, o, blocks, stream);
-}
-
-// rt_probe_segment: the node / primitive placement the trace kernel uses (`wide`, as launch_hit4)
+// rt_probe_segment: placed as launch_hit4
 hipError_t launch_probe(const DScene& S, bool wide, const double* rays, int n, uint64_t seed, uint32_t sample,
                         uint32_t draw, void* out, hipStream_t stream) {
   const int blocks = (n + kHitThreads - 1) / kHitThreads;
   if (blocks == 0) return hipSuccess;
   ProbeOut* o = static_cast<ProbeOut*>(out);
-  if (wide) {
-    if (S.n_lds_prims > 0) return launch_probe_m<kSceneLds>(S, rays, n, seed, sample, draw, o, blocks, stream);
-    return launch_probe_m<kNodesLds>(S, rays, n, seed, sample, draw, o, blocks, stream);
-  }
-  switch (node_mode4(S)) {
-    case kNodesLds: return launch_probe_m<kNodesLds>(S, rays, n, seed, sample, draw, o, blocks, stream);
-    case kNodesGlobal: return launch_probe_m<kNodesGlobal>(S, rays, n, seed, sample, draw, o, blocks, stream);
-    default: return launch_probe_m<kNodesMixed>(S, rays, n, seed, sample, draw, o, blocks, stream);
-  }
+  return dispatch_placement<kHitThreads>(S, wide, [&](auto, auto mode) {
+    constexpr int M = decltype(mode)::value;
+    auto go = [&](auto kernel, bool ext) {
+      return launch_block(kernel, blocks, kHitThreads, block_lds_bytes<M>(S, node4_bytes(ext), kHitThreads), stream, S,
+                          rays, n, seed, sample, draw, o);
+    };
+    return S.exts ? go(probe_kernel<M, true>, true) : go(probe_kernel<M, false>, false);
+  });
 }
 
 hipError_t launch_reduce(const double* partial, int n_chunks, int n_tiles_rank, int tiles_x, int ty0, int tile_rank,
