@@ -620,6 +620,8 @@ int rt_scene_lights_host(const rt_scene_desc* scene, int32_t* n_lights, int32_t*
  *             renderer's scatter attenuation there (rt_probe.attenuation: the texture value, unit(value) for a
  *             FairyLight), on the path's draws D, D+1, ...:
  *     pick      xi0 = draw D;  k = min((int)(xi0 * (double)L), L - 1): light k of the list.
+ *               (With a light grid set by rt_scene_light_pick, below: k = the smallest index with xi0 < cdf_k in
+ *               the row of x's cell, p = cdf_k - (k ? cdf_(k-1) : 0.0).)
  *     rect      xi1, xi2 = draws D+1, D+2;  y[d1] = d1_min + xi1 * (d1_max - d1_min),
  *               y[d2] = d2_min + xi2 * (d2_max - d2_min), y[axis] = offset, with (d1, d2, axis) = (x, y, z) for
  *               RECT_XY, (y, z, x) for RECT_YZ, (x, z, y) for RECT_XZ (geometry/rect.rs).
@@ -636,6 +638,7 @@ int rt_scene_lights_host(const rt_scene_desc* scene, int32_t* n_lights, int32_t*
  *               light than 2^-20 of the distance between vertex and light sample is ignored.
  *     value     Le = colour (DiffuseLight) or colour * cy per channel (FairyLight; lighting.rs:59-65 for the ray
  *               (x, w));  g = ((cx * cy) / d2) * ((area * (double)L) / pi);  direct_c = (a_c * Le_c) * g.
+ *               (With a light grid: g = ((cx * cy) / d2) * ((area / p) / pi).)
  *   Only + - * /, a correctly rounded sqrt, comparisons and selects, in the order written (no fused
  *   multiply-add): a restatement in IEEE binary64 gives the same bits wherever `a` needs no libm function.
  *   The light sample's density is 1 / (L * area) per unit area, so E[direct] is the vertex's exact direct
@@ -687,6 +690,9 @@ int rt_render_direct_device(rt_ctx* ctx, const rt_camera* cam, const rt_render_p
  *               value_c = (a_c * Le_c) * g with
  *                 RT_NEE_MIS clear: g = ((cx * cy) / d2) * ((area * (double)L) / pi);
  *                 RT_NEE_MIS set:   gs = ((cx * cy) / d2) / pi;  pl = 1.0 / (area * (double)L);  g = gs / (pl + gs).
+ *               (With a light grid set by rt_scene_light_pick, below: the grid's pick, and
+ *                 RT_NEE_MIS clear: g = ((cx * cy) / d2) * ((area / p) / pi);
+ *                 RT_NEE_MIS set:   pl = p / area, here and, with p_j(cell_prev), in `emission` above.)
  *               rad += att * value (per channel).  Remembered for the next hit: that a sample was taken (cut and
  *               occluded ones included) and cx_prev = ((n.x*d'.x + n.y*d'.y) + n.z*d'.z) / sqrt(len2(d')) with
  *               len2(d') = (d'.x*d'.x + d'.y*d'.y) + d'.z*d'.z.  Metal and dielectric vertices take no
@@ -708,6 +714,81 @@ int rt_render_nee(rt_ctx* ctx, const rt_camera* cam, const rt_render_params* par
                   double* accum_host /* [H][W][3] */);
 int rt_render_nee_device(rt_ctx* ctx, const rt_camera* cam, const rt_render_params* params, int32_t flags,
                          double* accum_dev, void* stream);
+
+/* ---- the spatially weighted light pick ---------------------------------------------
+ * Added within ABI 11 like the light list: purely additive, RT_ABI_VERSION stays 11.
+ *
+ * A scene-level setting that rt_render_direct and rt_render_nee (host and _device forms) read: with it the one
+ * light per vertex is picked, on the same draw D, from a table row that depends on where the vertex lies, in
+ * place of the uniform pick.  rt_scene_upload resets it to the uniform pick, so a caller that never sets it sees
+ * no change.
+ *
+ * Light grid of a list of L >= 1 lights and `cells` in 1 ... 64.  IEEE binary64 throughout; only + - * /,
+ * comparisons and selects, in the order written (no libm function, no fused multiply-add).
+ *   box of light j   sphere: lo_a = c_a - r, hi_a = c_a + r, centre c;  rho2_j = r * r.
+ *                    rect (d1, d2, axis as in rt_render_direct): h1 = (d1_max - d1_min) * 0.5,
+ *                    h2 = (d2_max - d2_min) * 0.5; lo = (d1_min, d2_min, offset), hi = (d1_max, d2_max, offset),
+ *                    centre = (d1_min + h1, d2_min + h2, offset) on (d1, d2, axis);  rho2_j = h1 * h1 + h2 * h2.
+ *   grid box         lo_a = the least box lo_a, hi_a = the greatest box hi_a, taken in list order
+ *                    (lo_a = b < lo_a ? b : lo_a; hi_a = b > hi_a ? b : hi_a, starting from light 0's).
+ *   dimensions       ext_a = hi_a - lo_a;  ext_max = the greatest of ext_x, ext_y, ext_z (e > m ? e : m in this
+ *                    order).  n_a = 1 if !(ext_a > 0); else f = (double)cells * (ext_a / ext_max) and
+ *                    n_a = f < (double)cells ? 1 + (int)f : cells, which is min(cells, 1 + (int)f).
+ *                    size_a = ext_a / (double)n_a.  A table of n_x * n_y * n_z * L > 2^22 entries is refused.
+ *                    cells = 1 is one row: a position-independent, power-weighted pick.
+ *   cell (ix,iy,iz)  row (iz * n_y + iy) * n_x + ix of L entries;  cell_lo_a = lo_a + (double)i_a * size_a,
+ *                    cell_hi_a = lo_a + (double)(i_a + 1) * size_a.
+ *   weights          s_j = (colour0 + colour1) + colour2;  Phi_j = area_j * (s_j > 0 ? s_j : 0)  (a NaN gives 0).
+ *                    diag2 = (size_x * size_x + size_y * size_y) + size_z * size_z.
+ *                    per axis t = cell_lo_a - c_a; t = t > 0 ? t : 0; e = c_a - cell_hi_a; d_a = e > t ? e : t.
+ *                    D2 = (d_x * d_x + d_y * d_y) + d_z * d_z;  m = rho2_j + diag2;
+ *                    w_j = Phi_j / (D2 > m ? D2 : m);  W = ((0 + w_0) + w_1) + ... in list order.
+ *   row              if W > 0 and W < +inf:  p_j = ((w_j / W) * 0.875) + (0.125 / (double)L);
+ *                    cdf_j = cdf_(j-1) + p_j from cdf_(-1) = 0, in list order.
+ *                    otherwise (W is 0, +inf or a NaN):  cdf_j = (double)(j + 1) / (double)L.
+ *                    Then cdf_(L-1) = 1.0 exactly.
+ *   The evenly spread eighth keeps every p_j >= 0.125 / L > 0, whatever the colours (0, negative, inf, NaN), and
+ *   bounds every estimate at 8 times the uniform pick's.
+ * Pick at a vertex x (a device function of its own, csrc/rt/light_pick.h):
+ *   cell        per axis inv_a = n_a == 1 ? 0 : (double)n_a / (hi_a - lo_a);  q = (x_a - lo_a) * inv_a;
+ *               i_a = !(q >= 0) ? 0 : q >= (double)n_a ? n_a - 1 : (int)q  (a NaN gives 0; a vertex outside the
+ *               box takes the border cell: every row is a distribution over all L lights, so this is unbiased).
+ *   light       xi0 = draw D;  k = the smallest index with xi0 < cdf_k in the cell's row (a lower-bound binary
+ *               search whose trip count depends on L alone; L - 1 if there is none: xi0 >= 1 or a NaN).
+ *   probability p = cdf_k - (k ? cdf_(k-1) : 0.0): up to rounding, the probability with which the search returns k.
+ * rt_render_direct and rt_render_nee with the grid pick: everything as defined above, except
+ *   pick        the light is k above, and pl = p / area in place of 1 / (area * (double)L):
+ *   value       RT_NEE_MIS clear (and rt_render_direct): g = ((cx * cy) / d2) * ((area / p) / pi);
+ *               RT_NEE_MIS set: gs = ((cx * cy) / d2) / pi;  pl = p / area;  g = gs / (pl + gs).
+ *   emission    (rt_render_nee, RT_NEE_MIS set) the weight of a listed hit on light j uses
+ *               pl = p_j(cell_prev) / area_j, p_j(c) = cdf_j - (j ? cdf_(j-1) : 0.0) in row c, where cell_prev is
+ *               the cell of the vertex that took the light sample.
+ *   With L = 1 every row is {1.0}, p = 1.0, and the frames equal the uniform pick's bit for bit.
+ * Unbiased because every p_j > 0 in every row, the pick's probability is the p the estimator divides by, and the
+ * row used depends on the vertex alone. */
+typedef struct rt_light_grid {
+  int32_t n[3];     /* cells along x, y, z (all 0 when n_lights == 0) */
+  int32_t n_lights; /* L */
+  double lo[3];     /* the grid's box */
+  double hi[3];
+} rt_light_grid;
+/* The grid of a description's light list, without a device.  `info` (not NULL) receives the dimensions and the
+ * box; cdf (may be NULL) has room for n[0] * n[1] * n[2] * n_lights doubles and receives the rows.  A scene
+ * without a listed light: RT_OK, info all zero, nothing written to cdf.  RT_E_INVALID: a NULL or invalid scene,
+ * cells outside 1 ... 64, a table of more than 2^22 entries. */
+int rt_light_grid_host(const rt_scene_desc* scene, int32_t cells, rt_light_grid* info, double* cdf);
+/* Sets the light pick of the uploaded scene.  cells = 0: the uniform pick.  cells in 1 ... 64: builds the grid of
+ * the scene's light list, uploads it, and makes rt_render_direct / rt_render_nee use it until the next
+ * rt_scene_upload or rt_scene_light_pick.  `info` (may be NULL) receives what rt_light_grid_host would report
+ * (all zero for cells = 0).  A scene without a listed light: RT_OK; nothing is ever picked.  RT_E_INVALID: no
+ * uploaded scene, cells < 0 or > 64, a table of more than 2^22 entries (the setting is then left as it was).
+ * Blocks until work queued on the context's stream has finished, since it replaces what that work reads. */
+int rt_scene_light_pick(rt_ctx* ctx, int32_t cells, rt_light_grid* info);
+/* Runs only the pick, on the device, for n points (points [n][3], xi [n]) in the grid last set by
+ * rt_scene_light_pick: light[i] = k and prob[i] = p for the vertex points[i] and the draw xi[i].  A test entry
+ * point like rt_probe_segment.  RT_E_INVALID: no uploaded scene, the uniform pick is set, the scene lists no
+ * light, n < 0, a NULL buffer with n > 0.  Blocks. */
+int rt_light_pick_at(rt_ctx* ctx, int32_t n, const double* points, const double* xi, int32_t* light, double* prob);
 
 #ifdef __cplusplus
 }

@@ -28,6 +28,8 @@
 // --nee [--nee-mis 0|1]: the light-sampling path integrator (rt_render_nee; --nee-mis 1, the default, weights
 // light sample and scatter by the balance heuristic) in place of the colour render, with the usual -s / -m;
 // the same restrictions as --direct, and not together with it.
+// --light-grid N (with --nee or --direct): the spatially weighted light pick (rt_scene_light_pick) with N cells,
+// 1 ... 64, along the light grid's longest axis; 0, the default, is the uniform pick.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -63,6 +65,8 @@ struct Args {
   int direct_chain = 8;
   bool nee = false;  // --nee: the light-sampling path integrator in place of the colour render
   int nee_mis = 1;
+  int light_grid = 0;  // --light-grid N: the light pick of --nee / --direct (0: uniform)
+  bool light_grid_given = false;
   double fov = 20.0, focal = 1.0, aperture = 0.001;
   bool night = false, single_threaded = false;
   unsigned long long seed = 0x5EED;
@@ -82,7 +86,8 @@ struct Args {
                "         --denoise [N] --denoise-chain K --denoise-variance (with --adaptive)\n"
                "         --ao RADIUS|inf --ao-chain K\n"
                "         --direct --direct-chain K\n"
-               "         --nee --nee-mis 0|1\n");
+               "         --nee --nee-mis 0|1\n"
+               "         --light-grid N (with --nee or --direct; 0 ... 64 cells, 0 = uniform pick)\n");
   std::exit(2);
 }
 
@@ -361,7 +366,13 @@ int render_scene(const Args& a, const rt_scene_desc* desc, const rt_camera& cam)
       return 1;
     }
     return 0;
-  } else if (a.direct) {
+  }
+  if ((a.direct || a.nee) && a.light_grid > 0 && (st = rt_scene_light_pick(ctx, a.light_grid, nullptr))) {
+    std::fprintf(stderr, "error: --light-grid: %s\n", rt_last_error(ctx));
+    rt_destroy(ctx);
+    return 1;
+  }
+  if (a.direct) {
     // the direct-lighting pass in place of the colour render: emission + direct through the tonemap
     std::vector<double> direct(n);
     accum.resize(n);
@@ -596,6 +607,10 @@ int main(int argc, char** argv) {
       const std::string v = next();
       a.nee_mis = v == "0" ? 0 : v == "1" ? 1 : -1;
     }
+    else if (s == "--light-grid") {
+      a.light_grid = std::atoi(next().c_str());
+      a.light_grid_given = true;
+    }
     else if (s == "--partition") {
       const std::string v = next();
       if (v == "tiles") a.partition = RT_PARTITION_TILES;
@@ -649,6 +664,9 @@ int main(int argc, char** argv) {
     usage("--direct replaces the colour render: no --adaptive, no --denoise, no --ao");
   if (a.direct && !a.dump_accum.empty()) usage("--direct frames are not checkpointed (--dump-accum)");
   if (a.direct_chain < 0) usage("--direct-chain K >= 0");
+
+  if (a.light_grid_given && !(a.nee || a.direct)) usage("--light-grid sets the light pick of --nee or --direct");
+  if (a.light_grid < 0 || a.light_grid > 64) usage("--light-grid N in 0 ... 64");
 
   sh_scene* scene = nullptr;
   std::string cam_scene = a.scene;

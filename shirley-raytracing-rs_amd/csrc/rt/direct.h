@@ -6,6 +6,7 @@
 // path's own draws; the shadow ray goes through the any-hit walk occluded4 (occlusion.h).
 #pragma once
 
+#include "light_pick.h"
 #include "occlusion.h"
 
 namespace rt {
@@ -21,15 +22,26 @@ constexpr double kShadowTMax = 1.0 - 0x1p-20;
 // lands on.  MIS: the sample carries the balance-heuristic weight against the Lambertian scatter, whose density
 // in area measure at the light is gs = ((cx * cy) / d2) / pi, the light sample's being pl = 1 / (area * L):
 // g = (1 / pl) * (pl / (pl + gs)) * gs = gs / (pl + gs) in place of gs / pl (rt_render_nee, shirley_rt.h).
-template <int THREADS, int MODE, bool MIS>
+// PICK (light_pick.h): kPickGrid takes the light from the vertex's cell of `grid` on the same draw D, with
+// probability pk, so pl = pk / area (rt_scene_light_pick); `cell` receives the vertex's cell, which
+// the path integrator keeps for the weight of the hit its scatter lands on.  A uniform instance leaves it alone.
+template <int THREADS, int MODE, bool MIS, int PICK>
 __device__ __forceinline__ v3 direct_light(const DScene& S, const DNode4F* lds_nodes, const DPrim* lds_prims,
                                            const DLight* __restrict__ lights, int n_lights, Rng& rng, uint64_t seed,
                                            v3 x, v3 n, v3 a, unsigned* stk, unsigned& visits, unsigned& ptests,
-                                           bool& taken) {
+                                           bool& taken, const typename PickGrid<PICK>::type& grid, int& cell) {
   taken = true;
   const double nl = (double)n_lights;
-  const int pick = (int)(rng_next(rng, seed) * nl);
-  const DLight& L = lights[pick < n_lights - 1 ? pick : n_lights - 1];
+  int li;
+  double pk = 1.0;
+  if constexpr (PICK == kPickGrid) {
+    cell = light_cell(grid, x.x, x.y, x.z);
+    li = light_pick(grid, cell, n_lights, rng_next(rng, seed), pk);
+  } else {
+    const int pick = (int)(rng_next(rng, seed) * nl);
+    li = pick < n_lights - 1 ? pick : n_lights - 1;
+  }
+  const DLight& L = lights[li];
   const int geom = L.geometry;
   v3 y, u = V(0.0, 0.0, 0.0);
   if (geom == RT_GEOM_SPHERE) {
@@ -63,22 +75,24 @@ __device__ __forceinline__ v3 direct_light(const DScene& S, const DNode4F* lds_n
   double g;
   if (MIS) {
     const double gs = ((cx * cy) / d2) / kDirectPi;
-    const double pl = 1.0 / (L.area * nl);
+    const double pl = PICK == kPickGrid ? pk / L.area : 1.0 / (L.area * nl);
     g = gs / (pl + gs);
   } else {
-    g = ((cx * cy) / d2) * ((L.area * nl) / kDirectPi);
+    g = ((cx * cy) / d2) * ((PICK == kPickGrid ? L.area / pk : L.area * nl) / kDirectPi);
   }
   return scale(hmul(a, le), g);
 }
 
 // The plain form (rt_render_direct's estimator).
-template <int THREADS, int MODE>
+template <int THREADS, int MODE, int PICK>
 __device__ __forceinline__ v3 direct_light(const DScene& S, const DNode4F* lds_nodes, const DPrim* lds_prims,
                                            const DLight* __restrict__ lights, int n_lights, Rng& rng, uint64_t seed,
-                                           v3 x, v3 n, v3 a, unsigned* stk, unsigned& visits, unsigned& ptests) {
+                                           v3 x, v3 n, v3 a, unsigned* stk, unsigned& visits, unsigned& ptests,
+                                           const typename PickGrid<PICK>::type& grid) {
   bool taken;
-  return direct_light<THREADS, MODE, false>(S, lds_nodes, lds_prims, lights, n_lights, rng, seed, x, n, a, stk, visits,
-                                            ptests, taken);
+  int cell;
+  return direct_light<THREADS, MODE, false, PICK>(S, lds_nodes, lds_prims, lights, n_lights, rng, seed, x, n, a, stk,
+                                                  visits, ptests, taken, grid, cell);
 }
 
 }  // namespace rt

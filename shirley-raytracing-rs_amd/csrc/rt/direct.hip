@@ -5,10 +5,12 @@
 // camera ray and the dielectric chain to the feature vertex, the wave's marble for a Perlin albedo, so lanes of
 // an edge tile outside the image stay, idle, for that wave-wide step) that, at a Lambertian or FairyLight vertex,
 // calls direct_light (direct.h), whose shadow ray asks the any-hit walk occluded4 (occlusion.h).  The light table
-// is a kernel argument of its own.  No atomics, no inter-wave traffic.  Its block size and launch are the frame's
-// (pass_frame.h); the kernel spells the frame's device pieces out, because with any of them it runs 0.5 % slower
-// on the night frame (profiles/passframe/direct_pieces.json).
+// is a kernel argument of its own, and so is the light grid of a kPickGrid instance (light_pick.h, DESIGN.md §18;
+// the last argument, an empty record in the uniform instances).  No atomics, no inter-wave traffic.  Its block
+// size and launch are the frame's (pass_frame.h); the kernel spells the frame's device pieces out, because with
+// any of them it runs 0.5 % slower on the night frame (profiles/passframe/direct_pieces.json).
 // Reference scenes only (no book-2 records): EXT = false instances.
+// light_pick_kernel (rt_light_pick_at) runs the grid's pick alone, one point per lane.
 #include <hip/hip_runtime.h>
 
 #include "direct.h"
@@ -17,12 +19,13 @@
 
 namespace rt {
 
-template <int THREADS, int MODE>
+template <int THREADS, int MODE, int PICK>
 __global__ __launch_bounds__(THREADS) void direct_kernel(DScene S, DCamera C, uint64_t seed, int s_begin, int s_end,
                                                          int chain, int tiles_x, int n_tiles,
                                                          const DLight* __restrict__ lights, int n_lights,
                                                          double* __restrict__ emission,
-                                                         double* __restrict__ direct) {
+                                                         double* __restrict__ direct,
+                                                         const typename PickGrid<PICK>::type grid) {
   extern __shared__ unsigned char lds_raw[];
   const int tid = threadIdx.x;
   typedef DNode4F N4;
@@ -114,8 +117,8 @@ __global__ __launch_bounds__(THREADS) void direct_kernel(DScene S, DCamera C, ui
             a = unit(a);
           }
           if (n_lights > 0)
-            dl = direct_light<THREADS, MODE>(S, lds_nodes, lds_prims, lights, n_lights, rng, seed, h.point, h.normal,
-                                             a, stk, visits, ptests);
+            dl = direct_light<THREADS, MODE, PICK>(S, lds_nodes, lds_prims, lights, n_lights, rng, seed, h.point,
+                                                   h.normal, a, stk, visits, ptests, grid);
         }
       }
       se = se + em;
@@ -137,16 +140,46 @@ __global__ __launch_bounds__(THREADS) void direct_kernel(DScene S, DCamera C, ui
 }
 
 // rt_render_direct
+// rt_render_direct; `grid` (null: the uniform pick) is read only where n_lights > 0
 hipError_t launch_direct(const DScene& S, bool wide, const DCamera& C, uint64_t seed, int s_begin, int s_end, int chain,
-                         const DLight* lights, int n_lights, double* emission, double* direct, hipStream_t stream) {
+                         const DLight* lights, int n_lights, const DLightGrid* grid, double* emission, double* direct,
+                         hipStream_t stream) {
   if (S.exts) return hipErrorInvalidValue;  // (the caller refuses book-2 scenes)
   if (n_lights > 0 && !lights) return hipErrorInvalidValue;
+  if (grid && n_lights > 0 && !grid->cdf) return hipErrorInvalidValue;
   const TileGrid G = tile_grid(C);
   return dispatch_placement<kPassThreadsWide>(S, wide, [&](auto threads, auto mode) {
     constexpr int T = decltype(threads)::value, M = decltype(mode)::value;
-    return launch_block(direct_kernel<T, M>, G.blocks(T), T, block_lds_bytes<M>(S, node4_bytes(false), T), stream, S, C,
-                        seed, s_begin, s_end, chain, G.tiles_x, G.n_tiles, lights, n_lights, emission, direct);
+    auto go = [&](auto kernel, auto g) {
+      return launch_block(kernel, G.blocks(T), T, block_lds_bytes<M>(S, node4_bytes(false), T), stream, S, C, seed,
+                          s_begin, s_end, chain, G.tiles_x, G.n_tiles, lights, n_lights, emission, direct, g);
+    };
+    return grid && n_lights > 0 ? go(direct_kernel<T, M, kPickGrid>, *grid)
+                                : go(direct_kernel<T, M, kPickUniform>, NoLightGrid{});
   });
+}
+
+// rt_light_pick_at: a ray-batch-style kernel (one point per lane, a kHitThreads block) that runs only the pick.
+__global__ __launch_bounds__(kHitThreads) void light_pick_kernel(const DLightGrid grid, int n_lights, int n,
+                                                                 const double* __restrict__ points,
+                                                                 const double* __restrict__ xi,
+                                                                 int32_t* __restrict__ light,
+                                                                 double* __restrict__ prob) {
+  const int i = blockIdx.x * kHitThreads + (int)threadIdx.x;
+  if (i >= n) return;
+  const double* p = points + (size_t)i * 3;
+  const int cell = light_cell(grid, p[0], p[1], p[2]);
+  double pk;
+  light[i] = light_pick(grid, cell, n_lights, xi[i], pk);
+  prob[i] = pk;
+}
+
+hipError_t launch_light_pick(const DLightGrid& grid, int n_lights, int n, const double* points, const double* xi,
+                             int32_t* light, double* prob, hipStream_t stream) {
+  if (n <= 0) return hipSuccess;
+  if (n_lights < 1 || !grid.cdf || !points || !xi || !light || !prob) return hipErrorInvalidValue;
+  return launch_block(light_pick_kernel, (n + kHitThreads - 1) / kHitThreads, kHitThreads, 0, stream, grid, n_lights, n,
+                      points, xi, light, prob);
 }
 
 }  // namespace rt

@@ -11,7 +11,9 @@
 // added in order with no atomics and no inter-wave traffic.  Lanes outside the image and lanes out of samples
 // stay in the loop, idle, for the wave-wide steps; the loop ends when the wave's last lane is done, and at the
 // latest after (s_end - s_begin) * max_depth iterations — one segment per live lane per iteration cannot
-// take more.  The light table and the primitive -> light table are kernel arguments of their own.
+// take more.  The light table and the primitive -> light table are kernel arguments of their own, and so is the
+// light grid of a kPickGrid instance (light_pick.h, DESIGN.md §18: the last argument, an empty record in the
+// uniform instances), whose path state holds one more integer: the cell of the vertex that took the light sample.
 #include <hip/hip_runtime.h>
 
 #include "direct.h"
@@ -20,12 +22,13 @@
 
 namespace rt {
 
-template <int THREADS, int MODE, bool MIS>
+template <int THREADS, int MODE, bool MIS, int PICK>
 __global__ __launch_bounds__(THREADS) void nee_kernel(DScene S, DCamera C, uint64_t seed, int s_begin, int s_end,
                                                       int max_depth, int tiles_x, int n_tiles,
                                                       const DLight* __restrict__ lights, int n_lights,
                                                       const int32_t* __restrict__ prim_light,
-                                                      double* __restrict__ accum) {
+                                                      double* __restrict__ accum,
+                                                      const typename PickGrid<PICK>::type grid) {
   extern __shared__ unsigned char lds_raw[];
   const BlockLds<DNode4F> L = carve_block_lds<MODE, DNode4F>(S, lds_raw);
   stage_nodes4<MODE>(S, L.nodes, L.prims);
@@ -38,10 +41,12 @@ __global__ __launch_bounds__(THREADS) void nee_kernel(DScene S, DCamera C, uint6
   unsigned long long steps = 0;
 #endif
   // the lane's path: sample s, segment k, ray (o, d), attenuation, radiance; prev / cx_prev: the last vertex
-  // took a light sample, and the cosine of its scatter direction there
+  // took a light sample, and the cosine of its scatter direction there; cell_prev: that vertex's cell of the
+  // light grid (a kPickGrid instance's only)
   int s = s_begin, k = 1;
   bool fresh = true, prev = false;
   double cx_prev = 0.0;
+  int cell_prev = 0;
   Rng rng{pix, (uint32_t)s_begin, 0u, 0u, 0u};
   v3 o = V(0.0, 0.0, 0.0), d = V(1.0, 1.0, 1.0);
   v3 att = V(1.0, 1.0, 1.0), rad = V(0.0, 0.0, 0.0), sum = V(0.0, 0.0, 0.0);
@@ -114,7 +119,11 @@ __global__ __launch_bounds__(THREADS) void nee_kernel(DScene S, DCamera C, uint6
               const double d2 = (h.t * h.t) * ld2;
               if (cx_prev > 0.0 && cy > 0.0) {
                 const double gs = ((cx_prev * cy) / d2) / kDirectPi;
-                const double pl = 1.0 / (lights[lj].area * (double)n_lights);
+                double pl;
+                if constexpr (PICK == kPickGrid)
+                  pl = light_prob(grid, cell_prev, n_lights, lj) / lights[lj].area;
+                else
+                  pl = 1.0 / (lights[lj].area * (double)n_lights);
                 ws = gs / (pl + gs);
               }
             } else {
@@ -129,8 +138,9 @@ __global__ __launch_bounds__(THREADS) void nee_kernel(DScene S, DCamera C, uint6
           prev = false;
           if ((mk == RT_MAT_LAMBERTIAN || mk == RT_MAT_FAIRY_LIGHT) && n_lights > 0 && k < max_depth) {
             // on the path's draws after the scatter's own; stands for segment k + 1's emission
-            const v3 dl = direct_light<THREADS, MODE, MIS>(S, L.nodes, L.prims, lights, n_lights, rng, seed, h.point,
-                                                           h.normal, mul, L.stk, visits, ptests, prev);
+            const v3 dl = direct_light<THREADS, MODE, MIS, PICK>(S, L.nodes, L.prims, lights, n_lights, rng, seed,
+                                                                 h.point, h.normal, mul, L.stk, visits, ptests, prev,
+                                                                 grid, cell_prev);
             rad = rad + hmul(att, dl);
             cx_prev = dot(h.normal, d) / sqrt_rn(len2(d));
           }
@@ -153,20 +163,24 @@ __global__ __launch_bounds__(THREADS) void nee_kernel(DScene S, DCamera C, uint6
   accum[p * 3 + 2] = sum.z;
 }
 
-// rt_render_nee
+// rt_render_nee; `grid` (null: the uniform pick) is read only where n_lights > 0
 hipError_t launch_nee(const DScene& S, bool wide, bool mis, const DCamera& C, uint64_t seed, int s_begin, int s_end,
-                      int max_depth, const DLight* lights, int n_lights, const int32_t* prim_light, double* accum,
-                      hipStream_t stream) {
+                      int max_depth, const DLight* lights, int n_lights, const DLightGrid* grid,
+                      const int32_t* prim_light, double* accum, hipStream_t stream) {
   if (S.exts) return hipErrorInvalidValue;  // (the caller refuses book-2 scenes)
   if (!accum || !prim_light || (n_lights > 0 && !lights)) return hipErrorInvalidValue;
+  if (grid && n_lights > 0 && !grid->cdf) return hipErrorInvalidValue;
   const TileGrid G = tile_grid(C);
   return dispatch_placement<kPassThreadsWide>(S, wide, [&](auto threads, auto mode) {
     constexpr int T = decltype(threads)::value, M = decltype(mode)::value;
-    auto go = [&](auto kernel) {
+    auto go = [&](auto kernel, auto g) {
       return launch_block(kernel, G.blocks(T), T, block_lds_bytes<M>(S, node4_bytes(false), T), stream, S, C, seed,
-                          s_begin, s_end, max_depth, G.tiles_x, G.n_tiles, lights, n_lights, prim_light, accum);
+                          s_begin, s_end, max_depth, G.tiles_x, G.n_tiles, lights, n_lights, prim_light, accum, g);
     };
-    return mis ? go(nee_kernel<T, M, true>) : go(nee_kernel<T, M, false>);
+    if (grid && n_lights > 0)
+      return mis ? go(nee_kernel<T, M, true, kPickGrid>, *grid) : go(nee_kernel<T, M, false, kPickGrid>, *grid);
+    return mis ? go(nee_kernel<T, M, true, kPickUniform>, NoLightGrid{})
+               : go(nee_kernel<T, M, false, kPickUniform>, NoLightGrid{});
   });
 }
 

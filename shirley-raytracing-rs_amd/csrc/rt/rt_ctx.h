@@ -12,6 +12,7 @@
 
 #include "../../../include/shirley_rt.h"
 #include "keycheck.h"
+#include "light_pick.h"
 #include "rccl_loader.h"
 #include "rt_launch.h"
 #include "rt_layout.h"
@@ -51,6 +52,13 @@ struct rt_ctx {
   DevBuf lights;
   DevBuf prim_light;  // rt_render_nee: device primitive number -> light-list index or -1, its own argument too
   std::vector<rt_light> light_list;
+  // rt_scene_light_pick: the host copies of the device records (the grid is built from them), the setting
+  // (light_cells == 0: the uniform pick), the uploaded rows and the grid as the kernels take it
+  std::vector<rt::DLight> light_dev;
+  int32_t light_cells = 0;
+  DevBuf light_cdf;
+  rt::DLightGrid light_grid{};
+  rt_light_grid light_grid_info{};
   int32_t n_unlisted_lights = 0;
   rt_scene_stats stats{};
   int blocks_per_cu = 0;
@@ -167,6 +175,10 @@ int render_window(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, co
 // order in which its refusals win; `name` is the entry point's, for the messages.
 inline int check_single_rank(rt_ctx* c, const rt_render_params* p, const char* name) {
   return p->tile_world != 1 ? fail(c, RT_E_INVALID, "%s: tile_world must be 1", name) : RT_OK;
+}
+// The light grid the light-sampling passes hand to their kernel: null while the pick is uniform.
+inline const DLightGrid* pass_light_grid(const rt_ctx* c) {
+  return c->light_cells > 0 && !c->light_list.empty() ? &c->light_grid : nullptr;
 }
 inline int pass_check(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, const char* name) {
   const int st = check_render_args(c, cam, p);

@@ -12,6 +12,7 @@
 #include "rt_layout.h"
 
 namespace rt {
+struct DLightGrid;  // light_pick.h
 // trace.hip
 hipError_t trace_occupancy(const DScene& S, int threads, int hop, int* blocks_per_cu);
 hipError_t launch_trace(const KParams& p, int blocks, int threads, int hop, hipStream_t stream);
@@ -54,11 +55,14 @@ hipError_t launch_ao(const DScene& S, bool wide, const DCamera& C, uint64_t seed
                      double radius, double* ao, hipStream_t stream);
 // direct.hip
 hipError_t launch_direct(const DScene& S, bool wide, const DCamera& C, uint64_t seed, int s_begin, int s_end, int chain,
-                         const DLight* lights, int n_lights, double* emission, double* direct, hipStream_t stream);
+                         const DLight* lights, int n_lights, const DLightGrid* grid, double* emission, double* direct,
+                         hipStream_t stream);
+hipError_t launch_light_pick(const DLightGrid& grid, int n_lights, int n, const double* points, const double* xi,
+                             int32_t* light, double* prob, hipStream_t stream);
 // nee.hip
 hipError_t launch_nee(const DScene& S, bool wide, bool mis, const DCamera& C, uint64_t seed, int s_begin, int s_end,
-                      int max_depth, const DLight* lights, int n_lights, const int32_t* prim_light, double* accum,
-                      hipStream_t stream);
+                      int max_depth, const DLight* lights, int n_lights, const DLightGrid* grid,
+                      const int32_t* prim_light, double* accum, hipStream_t stream);
 // trace_split.hip
 bool split_supported_nt(int nt);
 hipError_t split_prepare(const DScene& S, int nt, int* blocks_per_cu);

@@ -850,6 +850,121 @@ LightList list_lights(const rt_scene_desc* d) {
   return out;
 }
 
+// The light grid of include/shirley_rt.h (rt_scene_light_pick), step by step in the header's order: + - * /,
+// comparisons and selects only (no libm; the build never fuses a * b + c).
+int build_light_grid(const LightList& l, int32_t cells, bool want_cdf, LightGridTable* out) {
+  *out = LightGridTable{};
+  if (cells < 1 || cells > kLightGridMaxCells) return RT_E_INVALID;
+  const size_t L = l.dev.size();
+  if (L == 0) return RT_OK;
+  // per light: its box, its centre, rho2 and Phi
+  struct Item {
+    double lo[3], hi[3], c[3], rho2, phi;
+  };
+  std::vector<Item> items(L);
+  rt_light_grid& g = out->info;
+  for (size_t j = 0; j < L; ++j) {
+    const DLight& q = l.dev[j];
+    Item& it = items[j];
+    if (q.geometry == RT_GEOM_SPHERE) {
+      const double r = q.p[3];
+      for (int a = 0; a < 3; ++a) {
+        it.c[a] = q.p[a];
+        it.lo[a] = q.p[a] - r;
+        it.hi[a] = q.p[a] + r;
+      }
+      it.rho2 = r * r;
+    } else {
+      // (d1, d2, axis): RECT_XY (x, y, z), RECT_YZ (y, z, x), RECT_XZ (x, z, y)
+      const int d1 = q.geometry == RT_GEOM_RECT_YZ ? 1 : 0;
+      const int d2 = q.geometry == RT_GEOM_RECT_XY ? 1 : 2;
+      const int ax = 3 - d1 - d2;
+      const double h1 = (q.p[1] - q.p[0]) * 0.5, h2 = (q.p[3] - q.p[2]) * 0.5;
+      it.lo[d1] = q.p[0];
+      it.hi[d1] = q.p[1];
+      it.c[d1] = q.p[0] + h1;
+      it.lo[d2] = q.p[2];
+      it.hi[d2] = q.p[3];
+      it.c[d2] = q.p[2] + h2;
+      it.lo[ax] = it.hi[ax] = it.c[ax] = q.p[4];
+      it.rho2 = h1 * h1 + h2 * h2;
+    }
+    const double s = (q.color[0] + q.color[1]) + q.color[2];
+    it.phi = q.area * (s > 0.0 ? s : 0.0);  // (a NaN sum gives 0)
+    for (int a = 0; a < 3; ++a) {
+      g.lo[a] = (j == 0 || it.lo[a] < g.lo[a]) ? it.lo[a] : g.lo[a];
+      g.hi[a] = (j == 0 || it.hi[a] > g.hi[a]) ? it.hi[a] : g.hi[a];
+    }
+  }
+  // dimensions: `cells` along the longest axis, in proportion on the others, 1 on a flat one
+  double ext[3], ext_max = 0.0;
+  for (int a = 0; a < 3; ++a) {
+    ext[a] = g.hi[a] - g.lo[a];
+    ext_max = (a == 0 || ext[a] > ext_max) ? ext[a] : ext_max;
+  }
+  int64_t n_cells = 1;
+  double size[3];
+  for (int a = 0; a < 3; ++a) {
+    if (!(ext[a] > 0.0)) {
+      g.n[a] = 1;
+    } else {
+      const double f = (double)cells * (ext[a] / ext_max);
+      g.n[a] = f < (double)cells ? 1 + (int32_t)f : cells;  // = min(cells, 1 + (int)f); a NaN gives cells
+    }
+    size[a] = ext[a] / (double)g.n[a];
+    n_cells *= g.n[a];
+  }
+  g.n_lights = (int32_t)L;
+  if (n_cells * (int64_t)L > kLightGridMaxEntries) {
+    *out = LightGridTable{};
+    return RT_E_INVALID;
+  }
+  if (!want_cdf) return RT_OK;
+  out->cdf.resize((size_t)n_cells * L);
+  const double diag2 = (size[0] * size[0] + size[1] * size[1]) + size[2] * size[2];
+  const double floor_p = kLightPickUniform / (double)L;
+  std::vector<double> w(L);
+  double* row = out->cdf.data();
+  for (int32_t iz = 0; iz < g.n[2]; ++iz)
+    for (int32_t iy = 0; iy < g.n[1]; ++iy)
+      for (int32_t ix = 0; ix < g.n[0]; ++ix, row += L) {
+        const int32_t idx[3] = {ix, iy, iz};
+        double clo[3], chi[3];
+        for (int a = 0; a < 3; ++a) {
+          clo[a] = g.lo[a] + (double)idx[a] * size[a];
+          chi[a] = g.lo[a] + (double)(idx[a] + 1) * size[a];
+        }
+        double W = 0.0;
+        for (size_t j = 0; j < L; ++j) {
+          const Item& it = items[j];
+          double dd[3];
+          for (int a = 0; a < 3; ++a) {
+            double t = clo[a] - it.c[a];
+            t = t > 0.0 ? t : 0.0;
+            const double e = it.c[a] - chi[a];
+            dd[a] = e > t ? e : t;
+          }
+          const double D2 = (dd[0] * dd[0] + dd[1] * dd[1]) + dd[2] * dd[2];
+          const double m = it.rho2 + diag2;
+          w[j] = it.phi / (D2 > m ? D2 : m);
+          W = W + w[j];
+        }
+        // (W is 0, +inf or a NaN: the uniform row)
+        const bool weighted = W > 0.0 && W < std::numeric_limits<double>::infinity();
+        double acc = 0.0;
+        for (size_t j = 0; j < L; ++j) {
+          if (weighted) {
+            acc = acc + (((w[j] / W) * kLightPickWeighted) + floor_p);
+            row[j] = acc;
+          } else {
+            row[j] = (double)(j + 1) / (double)L;
+          }
+        }
+        row[L - 1] = 1.0;
+      }
+  return RT_OK;
+}
+
 int compile_scene(const rt_scene_desc* d, int32_t builder, const SceneTuning& tune, CompiledScene* out,
                   std::string* err) {
   int st = validate(d, err);

@@ -84,6 +84,20 @@ struct LightList {
 // Of a validated description.
 LightList list_lights(const rt_scene_desc* d);
 
+// The light grid of a light list (rt_scene_light_pick / rt_light_grid_host; include/shirley_rt.h has the build,
+// operation for operation): the public record and the rows, cell (iz * n[1] + iy) * n[0] + ix first to last.
+constexpr double kLightPickWeighted = 0.875;  // the share of a row that follows the weights w_j / W ...
+constexpr double kLightPickUniform = 0.125;   // ... and the share spread evenly, which keeps every p_j > 0
+constexpr int32_t kLightGridMaxCells = 64;
+constexpr int64_t kLightGridMaxEntries = (int64_t)1 << 22;
+struct LightGridTable {
+  rt_light_grid info{};
+  std::vector<double> cdf;  // n[0] * n[1] * n[2] rows of n_lights; stays empty when want_cdf is false
+};
+// RT_OK, or RT_E_INVALID for cells outside 1 ... 64 or a table of more than 2^22 entries.  No light: RT_OK, all
+// of `info` zero, no row.
+int build_light_grid(const LightList& l, int32_t cells, bool want_cdf, LightGridTable* out);
+
 // What rt_scene_upload copies to the device and records in the context.
 struct CompiledScene {
   std::vector<DNode> nodes;

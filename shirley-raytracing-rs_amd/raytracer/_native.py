@@ -131,6 +131,10 @@ class rt_light(C.Structure):  # the scene's light list (added within ABI 11)
                 ("area", C.c_double), ("color", _d3)]
 
 
+class rt_light_grid(C.Structure):  # the light grid of rt_scene_light_pick (added within ABI 11)
+    _fields_ = [("n", C.c_int32 * 3), ("n_lights", C.c_int32), ("lo", _d3), ("hi", _d3)]
+
+
 class rt_bvh_node(C.Structure):
     _fields_ = [("box", _d6), ("leaf", C.c_int32), ("lhs", C.c_int32), ("rhs", C.c_int32), ("pad", C.c_int32)]
 
@@ -233,6 +237,10 @@ RT_SIGNATURES = {
                                 C.c_void_p]),
     "rt_render_nee_device": (C.c_int, [C.c_void_p, C.POINTER(rt_camera), C.POINTER(rt_render_params), C.c_int32,
                                        C.c_void_p, C.c_void_p]),
+    # added within ABI 11: the spatially weighted light pick
+    "rt_light_grid_host": (C.c_int, [C.POINTER(rt_scene_desc), C.c_int32, C.POINTER(rt_light_grid), C.c_void_p]),
+    "rt_scene_light_pick": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(rt_light_grid)]),
+    "rt_light_pick_at": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 # every symbol declared in include/shirley_host.h

@@ -372,6 +372,27 @@ class Device:
                                                         N.RT_NEE_MIS if mis else 0, C.c_void_p(accum_ptr or None),
                                                         C.c_void_p(stream or None)))
 
+    def light_pick(self, cells: int) -> N.rt_light_grid:
+        """rt_scene_light_pick: how render_direct / render_nee pick their one light per vertex until the next
+        upload().  cells = 0: uniformly; 1 ... 64: from the light grid with that many cells along its longest
+        axis (include/shirley_rt.h).  Returns the grid's dimensions and box."""
+        info = N.rt_light_grid()
+        _check(self._h, N.rt_lib().rt_scene_light_pick(self._h, int(cells), C.byref(info)))
+        return info
+
+    def light_pick_at(self, points: np.ndarray, xi: np.ndarray):
+        """rt_light_pick_at: the device's pick alone -> (light [n] int32, prob [n] f64) for the vertices points[i]
+        and the draws xi[i], in the grid last set by light_pick."""
+        p = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+        x = np.ascontiguousarray(xi, dtype=np.float64).reshape(-1)
+        if len(p) != len(x):
+            raise ValueError("one draw per point")
+        light = np.zeros(max(1, len(p)), dtype=np.int32)
+        prob = np.zeros(max(1, len(p)), dtype=np.float64)
+        _check(self._h, N.rt_lib().rt_light_pick_at(self._h, len(p), p.ctypes.data, x.ctypes.data, light.ctypes.data,
+                                                     prob.ctypes.data))
+        return light[:len(p)], prob[:len(p)]
+
     def probe(self, rays: np.ndarray, seed: int, sample: int = 0, draw: int = 0):
         """One iteration of ray_color's loop (render.rs:30-46) per ray through the megakernel's device code
         (rt_probe_segment): ray i on the path key (seed, pixel = i, sample, draw) -> rt_probe array
@@ -448,6 +469,21 @@ def scene_digest(scene: Scene, bvh: str = "reference") -> int:
     if code:
         raise N.RtError(code, "rt_scene_digest_host: invalid scene")
     return d.value
+
+
+def light_grid_host(scene: Scene, cells: int):
+    """rt_light_grid_host -> (rt_light_grid, cdf): the light grid rt_scene_light_pick would build for this scene
+    (no device needed); cdf is [n[2]][n[1]][n[0]][n_lights] f64, empty when the scene lists no light."""
+    info = N.rt_light_grid()
+    code = N.rt_lib().rt_light_grid_host(scene.desc_ptr, int(cells), C.byref(info), None)
+    if code:
+        raise N.RtError(code, "rt_light_grid_host: invalid scene or cells, or a table of more than 2^22 entries")
+    cdf = np.zeros((info.n[2], info.n[1], info.n[0], info.n_lights), dtype=np.float64)
+    if cdf.size:
+        code = N.rt_lib().rt_light_grid_host(scene.desc_ptr, int(cells), C.byref(info), cdf.ctypes.data)
+        if code:
+            raise N.RtError(code, "rt_light_grid_host failed")
+    return info, cdf
 
 
 def tile_layout(camera: N.rt_camera, world: int):
