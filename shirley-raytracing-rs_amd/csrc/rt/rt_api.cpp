@@ -439,7 +439,7 @@ int render_window(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, co
       ks.scene.n_lds_mats = ks.scene.n_lds_texs = 0;
       HIP_TRY(c, launch_split(ks, c->split_nt, c->cu_count, s));
     } else {
-      HIP_TRY(c, launch_trace(kp, (int)nseg, c->place.mk_threads, c->place.hop_kind, s));
+      HIP_TRY(c, launch_trace(kp, (int)nseg, c->place.mk_threads, hop_instance(c->place), s));
     }
     HIP_TRY(c, hipEventRecord(c->pass_ev[2 * k + 1], s));
     if (k == passes - 1) HIP_TRY(c, hipEventRecord(c->ev[1], s));
@@ -575,7 +575,7 @@ int rt_scene_upload(rt_ctx* c, const rt_scene_desc* d, int32_t builder) {
   c->place = P;
 
   int bpc = 0;
-  HIP_TRY(c, trace_occupancy(S, P.mk_threads, P.hop_kind, &bpc));
+  HIP_TRY(c, trace_occupancy(S, P.mk_threads, hop_instance(P), &bpc));
   if (bpc < 1) return fail(c, RT_E_UNSUPPORTED, "trace kernel does not fit on a CU (LDS %lld B)", P.stack_bytes);
   c->blocks_per_cu = bpc;
   // wavefront extend block: its own LDS node count, no material tables

@@ -1063,7 +1063,8 @@ __device__ __forceinline__ int traverse(const DScene& S, const DNode* lds_nodes,
 // per-lane step counter of the instrumented build (a register of the calling kernel)
 #define g_trav_lane_steps trav_lane_steps_ref
 // event counters of the instrumented build: slot 2i += active lanes, slot 2i + 1 += 1 (per wave)
-static __device__ unsigned long long g_phase_ctr[64];
+constexpr int kPhaseEvents = 48;
+static __device__ unsigned long long g_phase_ctr[2 * kPhaseEvents];
 // histograms of the instrumented build: node visits per traversing lane, and per wave (its slowest lane)
 static __device__ unsigned long long g_visit_hist[64], g_wave_visit_hist[64];
 
@@ -1641,8 +1642,15 @@ __device__ __forceinline__ bool box_inward(int face, v3 d) {
   return (face & 1) ? da > 0.0 : da < 0.0;
 }
 typedef __attribute__((address_space(4))) const DGround GGround;
-__device__ __forceinline__ bool ground_hop(const DScene& S, const DPrim* lds_prims, const DMat* mats, GGround* g, v3 o, v3 d,
-                                           double t_min, double& t_best, int& best, int& face_best, bool& guarded) {
+// DOWN (the down pass, trace.hip HOP = 3): the result is kHopServed for such a hit, and kHopFound when the closest hit
+// in G is no dielectric's, on an xz-rect or a RectBox y face whose plane lies at least `gap` below Y (y <= g->y_down),
+// under the same origin, |d.y| and slope conditions: the proof's "hits on planes below Y" never asks what the hit's
+// material is, so that hit is the scene's closest too, and the caller shades it like a traversal's.  A hit of
+// another material on the plane Y itself is never found (a raised rect's padded box is the top there).
+constexpr int kHopRefused = 0, kHopServed = 1, kHopFound = 2;
+template <bool DOWN>
+__device__ __forceinline__ int ground_hop_t(const DScene& S, const DPrim* lds_prims, const DMat* mats, GGround* g, v3 o, v3 d,
+                                            double t_min, double& t_best, int& best, int& face_best, bool& guarded) {
   bool div_ok;  // every |d_i| in face_div's range
   const v3 inv = inv_dir(d, div_ok);
   const RaySigns ns = ray_signs(inv);
@@ -1676,11 +1684,23 @@ __device__ __forceinline__ bool ground_hop(const DScene& S, const DPrim* lds_pri
   // (faces 4 / 5: a RectBox's max / min y plane.  A hit at exactly t_min is not served: hit2's strict `t_max <= t_min`
   // then fails every box tested after the first accepted hit, so of two coplanar primitives of G the reference keeps
   // the one its own walk meets first — an order this loop does not follow)
-  if (best < 0 || (best & kTieBit) || face_best < 4 || !(t_best > t_min)) return false;
+  // (a RectBox y face; DOWN: or a rect of G — an xz-rect, face -1)
+  if (best < 0 || (best & kTieBit) || (DOWN ? face_best >= 0 && face_best < 4 : face_best < 4) || !(t_best > t_min))
+    return kHopRefused;
   const DPrim& pb = lds_prims[best];
   const double ay = fabs(d.y);
-  bool ok = mats[pb.material].kind == RT_MAT_DIELECTRIC && o.y >= g->y_lo && o.y <= g->y_hi && ay >= g->dy_min &&
-            ay <= 0x1p300 && d.x * d.x + d.z * d.z <= g->ratio2 * (d.y * d.y);
+  const bool diel = mats[pb.material].kind == RT_MAT_DIELECTRIC;
+  const bool slab_ok = o.y >= g->y_lo && o.y <= g->y_hi && ay >= g->dy_min && ay <= 0x1p300 &&
+                       d.x * d.x + d.z * d.z <= g->ratio2 * (d.y * d.y);
+  if constexpr (DOWN) {
+    if (!diel) {
+      // (a rect counts by the top of its padded box, leaf_box: a raised rect whose box makes the top plane lies on Y)
+      const double y = face_best < 0 ? pb.p[4] + 0.0001 : (face_best == 4 ? pb.p[4] : pb.p[1]);
+      return (slab_ok && y <= g->y_down) ? kHopFound : kHopRefused;
+    }
+    if (face_best < 4) return kHopRefused;  // (a dielectric rect is not served)
+  }
+  bool ok = diel && slab_ok;
   if (ok && (face_best == 4 ? pb.p[4] : pb.p[1]) == g->y_top) {
     // leaving through Y: the exit point's cell (the hit record's own point, o + t d)
     const int nx = g->nx;
@@ -1693,7 +1713,11 @@ __device__ __forceinline__ bool ground_hop(const DScene& S, const DPrim* lds_pri
       ok = !guarded;
     }
   }
-  return ok;
+  return ok ? kHopServed : kHopRefused;
+}
+__device__ __forceinline__ bool ground_hop(const DScene& S, const DPrim* lds_prims, const DMat* mats, GGround* g, v3 o, v3 d,
+                                           double t_min, double& t_best, int& best, int& face_best, bool& guarded) {
+  return ground_hop_t<false>(S, lds_prims, mats, g, o, d, t_min, t_best, best, face_best, guarded) != kHopRefused;
 }
 
 // Step-wise form for wf_extend4, where a ray's traversal state lives across loop iterations.

@@ -212,7 +212,7 @@ struct alignas(16) DGround {
   int32_t nx, nz;     // its cells (0: no guarded sphere)
   int32_t n, n_box;   // |G|; prim[0 .. n_box) are its RectBoxes, prim[n_box .. n) its rects
   int32_t prim[kGroundMaxPrims];
-  int32_t pad[2];
+  double y_down;      // Y - gap: the down pass finds a non-dielectric hit only on a plane at or below it
 };
 static_assert(sizeof(DGround) == 96, "DGround layout");
 // The guard cell of a coordinate along one axis of the rectangle (n cells from v0), or -1 outside it (and for a

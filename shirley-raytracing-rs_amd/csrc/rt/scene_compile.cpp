@@ -37,7 +37,10 @@ SceneTuning tuning_from_env() {
   t.no_lds_mats = getenv("SHIRLEY_NO_LDS_MATS") != nullptr;
   t.no_lds_perlin = getenv("SHIRLEY_NO_LDS_PERLIN") != nullptr;
   t.no_hop = getenv("SHIRLEY_NO_HOP") != nullptr;
-  if (const char* e = getenv("SHIRLEY_HOP")) t.hop_root = std::strcmp(e, "root") == 0;
+  if (const char* e = getenv("SHIRLEY_HOP")) {
+    t.hop_root = std::strcmp(e, "root") == 0;
+    t.hop_up = std::strcmp(e, "up") == 0;
+  }
   if (const char* e = getenv("SHIRLEY_SAH_BOXW")) t.sah_box_weight = atof(e);
   t.sah_binned = getenv("SHIRLEY_SAH_BINNED") != nullptr;
   t.wf_extend2 = getenv("SHIRLEY_WF_EXTEND2") != nullptr;
@@ -655,6 +658,7 @@ bool ground_stack(const std::vector<DPrim>& prims, int n_prims, std::vector<uint
   g.y_hi = top + tol;
   g.y_top = top;
   g.dy_min = std::max((2.0 * eta + 4.0 * tol) / 0.001, 0x1p-100);  // / the renderer's t_min (render.rs:30)
+  g.y_down = top - gap;
   g.ratio2 = ratio * ratio;
   g.n = (int32_t)n_g;
   g.n_box = (int32_t)boxes.size();
@@ -776,6 +780,19 @@ int plan_placement(const rt_scene_desc* d, int32_t placement, const SceneTuning&
   // ... by the scene's ground stack where it has one (SHIRLEY_HOP=root: never), else by a first-node visit
   P.hop_kind = !P.hop_pass ? 0 : (!tune.hop_root && ground_stack(cs.prims, d->n_objects, cs.ground)) ? 2 : 1;
   if (P.hop_kind != 2) cs.ground.clear();
+  // ... and, before the sampler, the downward hops too (trace.hip, HOP = 3) where the stack holds a primitive the
+  // down pass can find: one of another material on a plane at least `gap` below Y (SHIRLEY_HOP=up: never)
+  P.hop_down = false;
+  if (P.hop_kind == 2 && !tune.hop_up) {
+    DGround g;
+    std::memcpy(&g, cs.ground.data(), sizeof g);
+    for (int i = 0; i < g.n && !P.hop_down; ++i) {
+      const DPrim& q = cs.prims[g.prim[i]];
+      if (cs.mats[q.material].kind == RT_MAT_DIELECTRIC) continue;
+      // (a rect by the top of its padded box, as ground_hop_t does: a raised rect that makes the top plane is on Y)
+      P.hop_down = i < g.n_box ? (q.p[1] <= g.y_down || q.p[4] <= g.y_down) : q.p[4] + 0.0001 <= g.y_down;
+    }
+  }
 
   // wavefront extend block: its own (larger) stack area, the rest of LDS for nodes
   const long long wf_stack = (long long)wf_extend_lds(0, P.stack_depth);

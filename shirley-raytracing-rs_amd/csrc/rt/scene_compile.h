@@ -32,6 +32,7 @@ struct SceneTuning {
   bool no_lds_perlin = false;   // SHIRLEY_NO_LDS_PERLIN
   bool no_hop = false;          // SHIRLEY_NO_HOP
   bool hop_root = false;        // SHIRLEY_HOP=root: the first-node hop pass where the ground-stack one would run
+  bool hop_up = false;          // SHIRLEY_HOP=up: the ground-stack pass without its down pass (ScenePlacement.hop_down)
   double sah_box_weight = 4.0;  // SHIRLEY_SAH_BOXW=<c>
   bool sah_binned = false;      // SHIRLEY_SAH_BINNED
   bool wf_extend2 = false;      // SHIRLEY_WF_EXTEND2
@@ -57,7 +58,12 @@ struct ScenePlacement {
   int split_refill = 0;         // SceneTuning.split_refill
   bool hop_pass = false;        // the megakernel runs its instances with the hop pass (trace.hip)
   int hop_kind = 0;             // ... of which kind (rt_scene_stats.hop_kind): 1 first-node visit, 2 ground stack
+  bool hop_down = false;        // hop_kind 2 with the down pass before the sampler (trace.hip, HOP = 3)
 };
+
+// The megakernel's HOP instance of a placement (rt_launch.h launch_trace, trace_occupancy): hop_kind, or 3 for the
+// ground-stack pass with the down pass.
+inline int hop_instance(const ScenePlacement& P) { return P.hop_kind == 2 && P.hop_down ? 3 : P.hop_kind; }
 
 // The plan's fields of the megakernel's device scene record.
 inline void place_scene(const ScenePlacement& P, DScene& S) {

@@ -61,7 +61,8 @@ constexpr int kNarrowWaves = RT_NARROW_WAVES;
 // LIST: the launch's tiles come from DWork.tile_list (an adaptive step, adaptive.h) — separate instances, so
 // that every other call runs the code it ran without the list.
 // HOP: the hop pass at the end of the iteration body (below) — 0: none; 1: by a visit of the tree's first node;
-// 2: from the scene's ground stack (ScenePlacement.hop_kind) — compiled only into the scene-in-LDS
+// 2: from the scene's ground stack (ScenePlacement.hop_kind); 3: the same with the down pass after the traversal
+// (ScenePlacement.hop_down) — compiled only into the scene-in-LDS
 // reference-scene instances that launch_trace picks for a scene with a dielectric RectBox (ScenePlacement.hop_pass),
 // so every other instance keeps its code.
 #ifndef RT_HOP_MIN_LANES
@@ -82,6 +83,46 @@ constexpr int kNarrowWaves = RT_NARROW_WAVES;
 #endif
 #ifndef RT_HOP2_MIN_LANES_B
 #define RT_HOP2_MIN_LANES_B 16
+#endif
+// HOP = 3 (a ground stack with a non-dielectric member below its coat, ScenePlacement.hop_down): HOP = 2's pass plus
+// the down pass between the traversal and the hit record (below).  The lane thresholds of its up to three runs —
+// 32 / 16 / 16 of a sweep from 8 / 8 / 8 to 48 / 16 / 16 — and those of step 5's two runs in this instance, whose
+// candidates the down pass changes: 24 / 16 of {20 / 16, 24 / 8, 24 / 16, 24 / 24, 32 / 16} re-swept at 32 / 16 / 16
+// (20 / 16 is +0.3 %, inside the sweep's spread).
+#ifndef RT_HOPD_MIN_LANES_A
+#define RT_HOPD_MIN_LANES_A 32
+#endif
+#ifndef RT_HOPD_MIN_LANES_B
+#define RT_HOPD_MIN_LANES_B 16
+#endif
+#ifndef RT_HOPD_MIN_LANES_C
+#define RT_HOPD_MIN_LANES_C 16
+#endif
+#ifndef RT_HOP3_MIN_LANES_A
+#define RT_HOP3_MIN_LANES_A RT_HOP2_MIN_LANES_A
+#endif
+#ifndef RT_HOP3_MIN_LANES_B
+#define RT_HOP3_MIN_LANES_B RT_HOP2_MIN_LANES_B
+#endif
+#ifdef RT_HOP_SERVE_SHARED
+// A/B only: the serve body of the HOP = 3 instances as one call that the down pass and step 5' both
+// reach, instead of an inlined copy at each site.  Not built by default: the two inlined sites measured faster.
+struct ServeOut {
+  v3 o, d;
+  uint32_t draw, c2, c3;
+};
+__device__ __noinline__ ServeOut hop_serve_ool(const DPrim* lds_prims, const DMat* mats, int prim, int face, v3 o, v3 d,
+                                               double t, Rng rng, uint64_t seed_v) {
+  DScene S{};  // (hit_record reads the scene only for book-2 primitives)
+  const uint64_t seed = uniform64(seed_v);
+  const DPrim pr = lds_prims[prim];
+  Hit hh;
+  hit_record<false, false>(S, pr, face, o, d, t, rng, seed, hh);
+  const v3 ru = draw_diel(rng, seed);
+  const v3 ud = unit_fast(d);
+  shade_dielectric(mats[pr.material], ru, ud, rng, o, d, hh);
+  return ServeOut{o, d, rng.draw, rng.c2, rng.c3};
+}
 #endif
 template <int THREADS, int MODE, bool EXT, bool LIST = false, int HOP = 0>
 __global__ __launch_bounds__(THREADS, THREADS >= kTraceThreadsWide3 ? 1 : (EXT ? RT_NARROW_WAVES_EXT : kNarrowWaves))
@@ -190,9 +231,84 @@ void trace_kernel(KParams P) {
     h.front_face = false;
     PH_COUNT(6);
     n_seg += __popcll(__ballot(active));
+    // 1'. the down pass (HOP = 3).  A lane whose traversal hit is a dielectric primitive of the
+    // ground stack — the coat's top from above, mostly — is shaded here by the hop pass's serve body and asks the
+    // stack for its next hit (ground_hop_t<true>): a dielectric one, served, sends it round again (up to three
+    // runs, each with its own lane threshold); any other one that the stack's conditions prove the scene's closest —
+    // the rect under the coat — becomes the lane's hit of this iteration, recorded, sampled and shaded by the
+    // ordinary steps below; step 5 then takes the lane up through the coat.  One ground interaction is one
+    // iteration.  A lane that the stack cannot answer (or whose ray left the box it hit) waits: it keeps its new ray,
+    // takes no part in the steps below and traverses from the root next iteration, as it would have anyway.  The
+    // same functions of (seed, pixel, sample, draw index, ray) in each lane's own order as the iterations it
+    // replaces: frames and counters are bit-identical with and without the pass.
+    bool waiting = false;
+    if constexpr (HOP == 3) {
+      static_assert(MODE == kSceneLds && !EXT, "the hop pass is built for the scene-in-LDS reference-scene instances");
+      // (the pass's ballots need a wave-uniform point: this instance traverses here, not in the block below)
+      if (active)
+        prim = traverse4<THREADS, MODE, EXT>(S, lds_nodes, lds_prims, o, d, 0.001, t_best, face, stk, rng, seed, visits,
+                                             ptests RT_STAT_ARG(ph_lane_steps));
+      PH_STAMP(kPhTrav);
+      GGround* g = (GGround*)kblock(P.kconst)->ground;
+      bool pend = false;  // a dielectric hit of G in (prim, face, t_best), not shaded yet
+      if (active && prim >= 0 && mats[lds_prims[prim].material].kind == RT_MAT_DIELECTRIC)
+        for (int i = 0; i < g->n; ++i) pend = pend || g->prim[i] == prim;
+#if defined(RT_PHASE_TIMING) && !defined(RT_PHASE_NO_EVENTS)
+      if (pend) PH_COUNT(31);
+#endif
+#pragma unroll 1
+      for (int run = 0; run < 3; ++run) {
+        if (__popcll(__ballot(pend)) <
+            (run == 0 ? RT_HOPD_MIN_LANES_A : (run == 1 ? RT_HOPD_MIN_LANES_B : RT_HOPD_MIN_LANES_C)))
+          break;
+        int kind = kHopRefused;
+        if (pend) {
+          PH_COUNT(36 + 4 * run);
+          pend = false;
+#ifdef RT_HOP_SERVE_SHARED
+          const ServeOut so = hop_serve_ool(lds_prims, mats, prim, face, o, d, t_best, rng, seed);
+          o = so.o, d = so.d, rng.draw = so.draw, rng.c2 = so.c2, rng.c3 = so.c3;
+#else
+          const DPrim pr = lds_prims[prim];
+          Hit hh;
+          hit_record<false, false>(S, pr, face, o, d, t_best, rng, seed, hh);
+          const v3 ru = draw_diel(rng, seed);
+          const v3 ud = unit_fast(d);
+          shade_dielectric(mats[pr.material], ru, ud, rng, o, d, hh);  // (att * 1 = att, no emission)
+#endif
+          if (--depth_left <= 0) {
+            sum = sum + em;
+            active = false;  // takes its next sample in this iteration's step 2
+          }
+          // (who tries: a ray that runs on inside the box it hit, as in step 5', or downwards out of it, towards
+          // what lies under it in the stack; one that left upwards meets the spheres or the sky, and waits)
+          const bool inward = face < 0 || d.y < 0.0 || box_inward(face, d);
+          prim = -1;
+          waiting = active;
+          if (active && inward) {
+            double t_hop;
+            int p_hop, f_hop;
+            bool guarded;
+            kind = ground_hop_t<true>(S, lds_prims, mats, g, o, d, 0.001, t_hop, p_hop, f_hop, guarded);
+            if (kind != kHopRefused) {
+              prim = p_hop;
+              face = f_hop;
+              t_best = t_hop;
+              waiting = false;
+              pend = kind == kHopServed;
+              if (pend) PH_COUNT(37 + 4 * run); else PH_COUNT(38 + 4 * run);
+            }
+          }
+          if (waiting) PH_COUNT(39 + 4 * run);
+        }
+        n_seg += __popcll(__ballot(kind != kHopRefused));
+      }
+      PH_STAMP(kPhTrav);
+    }
     if (active) {
-      prim = traverse4<THREADS, MODE, EXT>(S, lds_nodes, lds_prims, o, d, 0.001, t_best, face, stk, rng, seed, visits,
-                                      ptests RT_STAT_ARG(ph_lane_steps));
+      if constexpr (HOP != 3)
+        prim = traverse4<THREADS, MODE, EXT>(S, lds_nodes, lds_prims, o, d, 0.001, t_best, face, stk, rng, seed, visits,
+                                        ptests RT_STAT_ARG(ph_lane_steps));
 #ifdef RT_PHASE_TIMING
     }  // (instrumented build: the traversal's stamp at a wave-uniform point)
     PH_STAMP(kPhTrav);
@@ -218,9 +334,29 @@ void trace_kernel(KParams P) {
       }
     }
     PH_STAMP(kPhRecord);
+#if defined(RT_PHASE_TIMING) && !defined(RT_PHASE_NO_EVENTS)
+    // (instrumented build: how the lanes that a pass between the traversal and the sampler could take — those whose
+    // traversal hit is a dielectric primitive of the ground stack — are bunched in the wave)
+    if constexpr (HOP == 2) {
+      bool dg = false;
+      if (hit && mk == RT_MAT_DIELECTRIC) {
+        GGround* g = (GGround*)kblock(P.kconst)->ground;
+        for (int i = 0; i < g->n; ++i) dg = dg || g->prim[i] == prim;
+      }
+      const int n_dg = __popcll(__ballot(dg));
+      if (dg) {
+        PH_COUNT(31);
+        if (n_dg >= 8) PH_COUNT(32);
+        if (n_dg >= 16) PH_COUNT(33);
+        if (n_dg >= 24) PH_COUNT(34);
+        if (n_dg >= 32) PH_COUNT(35);
+      }
+    }
+#endif
     // 2. the path ends at this segment when it misses (the sky) or meets a material that does not
     // scatter (diffuse light): known before shading, so the lane's next sample starts in this iteration
-    const bool ends = active && (!hit || mk == RT_MAT_DIFFUSE_LIGHT);
+    // (a lane left waiting by the down pass is neither: it holds a path and does nothing until the next iteration)
+    const bool ends = active && !waiting && (!hit || mk == RT_MAT_DIFFUSE_LIGHT);
     const bool free_lane = !active || ends;
     // a unit whose last sample ends here is published after shading (its sum is complete then)
     bool publish = false;
@@ -346,7 +482,7 @@ void trace_kernel(KParams P) {
     PH_STAMP(kPhMarble);
     // every draw of the iteration, by the wave: the scatter's random_in_unit_sphere, the dielectric's
     // uniform, a new sample's jitter and lens point
-    const bool scat = active && !ends;
+    const bool scat = active && !ends && !waiting;
     const int dk = regen ? kDrawCam
                          : (scat && need_r) ? kDrawSphere : (scat && mk == RT_MAT_DIELECTRIC) ? kDrawDiel : kDrawNone;
     double jx = 0.0, jy = 0.0;
@@ -364,7 +500,7 @@ void trace_kernel(KParams P) {
       camera_ray_drawn(kblock(P.kconst)->cam, jx, jy, rs, o, d);
     }
     PH_STAMP(kPhCamera);
-    if (active) {
+    if (active && !waiting) {
       bool alive, has_emit = false;
       v3 mul = V(1.0, 1.0, 1.0), emit = V(0.0, 0.0, 0.0);
       if (hit) {
@@ -464,7 +600,7 @@ void trace_kernel(KParams P) {
     // hop inside the coat, which no first-node visit can (the spheres' boxes start on the coat's top plane), so
     // the pass runs twice: the second run's candidates are the lanes the first one served, which turns "coat
     // bottom from below, coat top from inside" into one iteration.  Each run has its own lane threshold.
-    if constexpr (HOP == 2) {
+    if constexpr (HOP == 2 || HOP == 3) {
       static_assert(MODE == kSceneLds && !EXT, "the hop pass is built for the scene-in-LDS reference-scene instances");
       bool cand = active && !regen && hit;
       if (cand) cand = lds_prims[prim].kind != kPrimSphere;
@@ -477,7 +613,9 @@ void trace_kernel(KParams P) {
 #endif
 #pragma unroll 1
       for (int run = 0; run < 2; ++run) {
-        if (__popcll(__ballot(cand)) < (run ? RT_HOP2_MIN_LANES_B : RT_HOP2_MIN_LANES_A)) break;
+        if (__popcll(__ballot(cand)) < (HOP == 3 ? (run ? RT_HOP3_MIN_LANES_B : RT_HOP3_MIN_LANES_A)
+                                                 : (run ? RT_HOP2_MIN_LANES_B : RT_HOP2_MIN_LANES_A)))
+          break;
         bool serve = false;
         double t_hop = __builtin_inf();
         int p_hop = -1, f_hop = -1;
@@ -490,12 +628,20 @@ void trace_kernel(KParams P) {
         n_seg += __popcll(__ballot(serve));
         if (serve) {
           if (run) PH_COUNT(29); else PH_COUNT(27);
+#ifdef RT_HOP_SERVE_SHARED
+          if constexpr (HOP == 3) {
+            const ServeOut so = hop_serve_ool(lds_prims, mats, p_hop, f_hop, o, d, t_hop, rng, seed);
+            o = so.o, d = so.d, rng.draw = so.draw, rng.c2 = so.c2, rng.c3 = so.c3;
+          } else
+#endif
+          {
           const DPrim pr = lds_prims[p_hop];
           Hit hh;
           hit_record<false, false>(S, pr, f_hop, o, d, t_hop, rng, seed, hh);
           const v3 ru = draw_diel(rng, seed);
           const v3 ud = unit_fast(d);
           shade_dielectric(mats[pr.material], ru, ud, rng, o, d, hh);  // (att * 1 = att, no emission)
+          }
           if (--depth_left <= 0) {
             sum = sum + em;
             active = false;  // takes its next sample in the next iteration's step 2
@@ -962,7 +1108,7 @@ static hipError_t hit_prepare(const DScene& S) {
 }
 
 // Kernel instances: the wide block only with the whole (4-wide) BVH in LDS.  Also prepares the
-// rt_scene_hit kernel for the scene.  `hop` (ScenePlacement.hop_pass): the scene-in-LDS reference-scene instances
+// rt_scene_hit kernel for the scene.  `hop` (scene_compile.h hop_instance): the scene-in-LDS reference-scene instances
 // with the hop pass; an error for a scene that runs any other instance.
 hipError_t trace_occupancy(const DScene& S, int threads, int hop, int* blocks_per_cu) {
   hipError_t e = hit_prepare(S);
@@ -970,6 +1116,7 @@ hipError_t trace_occupancy(const DScene& S, int threads, int hop, int* blocks_pe
   if (hop && !(threads == kTraceThreadsWide && !S.exts && S.n_lds_prims > 0)) return hipErrorInvalidValue;
   if (threads == kTraceThreadsWide && !S.exts) {  // reference scenes only: book-2 scenes take kTraceThreadsWide3
     if (node_mode4(S) != kNodesLds) return hipErrorInvalidValue;
+    if (hop == 3) return occupancy_impl1<kTraceThreadsWide, kSceneLds, false, 3>(S, blocks_per_cu);
     if (hop == 2) return occupancy_impl1<kTraceThreadsWide, kSceneLds, false, 2>(S, blocks_per_cu);
     if (hop) return occupancy_impl1<kTraceThreadsWide, kSceneLds, false, 1>(S, blocks_per_cu);
     if (S.n_lds_prims > 0) return occupancy_impl1<kTraceThreadsWide, kSceneLds, false>(S, blocks_per_cu);
@@ -992,7 +1139,9 @@ hipError_t launch_trace(const KParams& p, int blocks, int threads, int hop, hipS
                                      p.scene.n_lds_mats, p.scene.n_lds_texs);
   if (hop && !(threads == kTraceThreadsWide && !p.scene.exts && p.scene.n_lds_prims > 0)) return hipErrorInvalidValue;
   if (threads == kTraceThreadsWide && !p.scene.exts) {
-    if (hop == 2)
+    if (hop == 3)
+      launch_trace2<kTraceThreadsWide, kSceneLds, false, 3>(p, blocks, lds, stream);
+    else if (hop == 2)
       launch_trace2<kTraceThreadsWide, kSceneLds, false, 2>(p, blocks, lds, stream);
     else if (hop)
       launch_trace2<kTraceThreadsWide, kSceneLds, false, 1>(p, blocks, lds, stream);
@@ -1145,15 +1294,23 @@ void timeline_dump() {
 #ifdef RT_PHASE_TIMING
 // instrumented build: print and clear the event counters (slot 2i: lane events, 2i + 1: wave events)
 void phase_counters_dump() {
-  unsigned long long h[64];
+  unsigned long long h[2 * kPhaseEvents];
   if (hipMemcpyFromSymbol(h, HIP_SYMBOL(g_phase_ctr), sizeof h) != hipSuccess) return;
   static const char* names[] = {"visit", "visit_with_leaves", "sphere_iter", "sphere_slab_pass", "rect_iter",
                                 "pop_iter", "segment_iter", "box_iter", "marble_round", "draws_coop_round",
                                 "unit_fetch", "camera_ray", "philox_A", "philox_B", "marble_sin", "hit_record",
                                 "checker_level", "dielectric", "metal", "lambertian", "sky", "diffuse_light",
                                 "reflectance", "traverse4", "publish", "tie_resolve", "hop_candidate", "hop_served",
-                                "hop2_candidate", "hop2_served", "hop_guarded"};
-  for (int i = 0; i < 31; ++i)
+                                "hop2_candidate", "hop2_served", "hop_guarded",
+                                // lanes whose traversal hit is a dielectric primitive of the ground stack, and those
+                                // of them in wave-iterations that hold at least 8 / 16 / 24 / 32 such lanes
+                                "down_hit", "down_hit_ge8", "down_hit_ge16", "down_hit_ge24", "down_hit_ge32",
+                                // the down pass (HOP = 3), per run: lanes tried, served, found, left waiting
+                                "down1_try", "down1_served", "down1_found", "down1_wait",
+                                "down2_try", "down2_served", "down2_found", "down2_wait",
+                                "down3_try", "down3_served", "down3_found", "down3_wait"};
+  static_assert(sizeof names / sizeof names[0] <= kPhaseEvents, "event slots");
+  for (int i = 0; i < (int)(sizeof names / sizeof names[0]); ++i)
     if (h[2 * i + 1])
       fprintf(stderr, "[phase-ev] %-18s lanes %.4g waves %.4g lanes/wave %.2f\n", names[i], (double)h[2 * i],
               (double)h[2 * i + 1], (double)h[2 * i] / (double)h[2 * i + 1]);
@@ -1164,10 +1321,10 @@ void phase_counters_dump() {
     for (int i = 1; i < 64; ++i)
       if (lh[i] || wh[i]) fprintf(stderr, "[phase-hist] %2d %.6g %.6g\n", i, (double)lh[i], (double)wh[i]);
   }
-  unsigned long long z[64] = {};
+  unsigned long long z[2 * kPhaseEvents] = {};
   (void)hipMemcpyToSymbol(HIP_SYMBOL(g_phase_ctr), z, sizeof z);
-  (void)hipMemcpyToSymbol(HIP_SYMBOL(g_visit_hist), z, sizeof z);
-  (void)hipMemcpyToSymbol(HIP_SYMBOL(g_wave_visit_hist), z, sizeof z);
+  (void)hipMemcpyToSymbol(HIP_SYMBOL(g_visit_hist), z, 64 * sizeof z[0]);
+  (void)hipMemcpyToSymbol(HIP_SYMBOL(g_wave_visit_hist), z, 64 * sizeof z[0]);
 }
 #endif
 

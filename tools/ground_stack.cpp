@@ -5,9 +5,10 @@
 //   ground_stack <case>[/KEY=VALUE[,KEY=VALUE...]] ...
 //     case       a builtin of sh_scene_builtin (random, cornell, ...) or @<file>: a scene saved as JSON
 //     KEY=VALUE  the upload-time tuning variable SHIRLEY_<KEY>, set for this case only
-// prints one JSON line per case.  Guard check: every cell against the distance from its rectangle to the nearest
-// contact point over all spheres (`cells_wrong`), and 256 points on and inside the guard circle of every guarded
-// sphere, which must all fall in marked cells (`points_free`).
+// prints one JSON line per case; `hop_down`: the launches take the down pass's instances (ScenePlacement.hop_down).
+// Guard check: every cell against the distance from its rectangle to the nearest contact point over all spheres
+// (`cells_wrong`), and 256 points on and inside the guard circle of every guarded sphere, which must all fall in
+// marked cells (`points_free`).
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -57,8 +58,9 @@ int main(int argc, char** argv) {
     rt::CompiledScene cs;
     std::string err;
     const int st = rt::compile_scene(sh_desc_view(desc), RT_BVH_SAH, tune, &cs, &err);
-    std::printf("{\"case\": \"%s\", \"status\": %d, \"hop_pass\": %d, \"hop_kind\": %d, \"stats_hop_kind\": %d", argv[a], st,
-                cs.place.hop_pass ? 1 : 0, cs.place.hop_kind, (int)cs.stats.hop_kind);
+    std::printf("{\"case\": \"%s\", \"status\": %d, \"hop_pass\": %d, \"hop_kind\": %d, \"stats_hop_kind\": %d, "
+                "\"hop_down\": %d", argv[a], st, cs.place.hop_pass ? 1 : 0, cs.place.hop_kind, (int)cs.stats.hop_kind,
+                cs.place.hop_down ? 1 : 0);
     if (st == 0 && cs.place.hop_kind == 2) {
       rt::DGround g;
       std::memcpy(&g, cs.ground.data(), sizeof g);
