@@ -269,6 +269,12 @@ const char* rt_last_error(const rt_ctx* ctx);
 /* ---- scene (replaces SceneBuilder::finalize, scene/mod.rs:111-137) --------------------------- */
 int rt_scene_upload(rt_ctx* ctx, const rt_scene_desc* scene, int32_t bvh_builder);
 int rt_scene_stats_get(rt_ctx* ctx, rt_scene_stats* out);
+/* Added within ABI 11 (purely additive): which megakernel instance the uploaded scene's hop pass runs — 0 none,
+ * 1 the first-node visit, 2 the ground stack's pass, 3 the same with the down pass before the sampler, 4 both by the
+ * closed-form next plane of a plane stack (a ground stack whose y planes lie a gap apart inside a common xz core;
+ * SHIRLEY_HOP=general at upload: 3 where 4 would be chosen).  rt_scene_stats.hop_kind is 2 for 2, 3 and 4: frames
+ * and counters are the same under every instance. */
+int rt_scene_hop_instance(rt_ctx* ctx, int32_t* out);
 /* ABI 6: 64-bit digest of the uploaded scene (its description and BVH builder; FNV-1a over every field),
  * and the same digest computed on the host from a description (no device needed).  Equal scenes give
  * equal digests; the multi-GPU calls compare them across ranks. */

@@ -425,6 +425,7 @@ int render_window(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, co
     kb.unit_counter = kp.unit_counter;
     kb.counters = kp.counters;
     kb.ground = c->place.hop_kind == 2 ? static_cast<const DGround*>(c->ground.p) : nullptr;
+    kb.planes = c->place.hop_planes ? static_cast<const DPlanes*>(c->planes.p) : nullptr;
     void* kdev = static_cast<KBlock*>(c->kcam.p) + k;
     HIP_TRY(c, hipMemcpyAsync(kdev, &kb, sizeof(KBlock), hipMemcpyHostToDevice, s));
     kp.kconst = (uint64_t)(uintptr_t)kdev;
@@ -504,7 +505,7 @@ int rt_destroy(rt_ctx* c) {
   if (!c) return RT_OK;
   (void)hipSetDevice(c->device);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
-  for (DevBuf* b : {&c->nodes, &c->nodes4, &c->prims, &c->mats, &c->texs, &c->perlin, &c->texels, &c->exts, &c->ground, &c->lights, &c->prim_light, &c->light_cdf, &c->partial, &c->kcam, &c->shutter0, &c->moments, &c->tile_list, &c->tile_err, &c->dn_a, &c->dn_b, &c->feat,
+  for (DevBuf* b : {&c->nodes, &c->nodes4, &c->prims, &c->mats, &c->texs, &c->perlin, &c->texels, &c->exts, &c->ground, &c->planes, &c->lights, &c->prim_light, &c->light_cdf, &c->partial, &c->kcam, &c->shutter0, &c->moments, &c->tile_list, &c->tile_err, &c->dn_a, &c->dn_b, &c->feat,
                     &c->accum, &c->counters, &c->unit_counter, &c->wf_pool, &c->wf_iters, &c->packed, &c->gathered,
                     &c->parts, &c->band, &c->digests})
     release(*b);
@@ -546,6 +547,11 @@ int rt_scene_upload(rt_ctx* c, const rt_scene_desc* d, int32_t builder) {
     if ((st = up(c->ground, cs.ground))) return st;
   } else {
     release(c->ground);
+  }
+  if (!cs.planes.empty()) {
+    if ((st = up(c->planes, cs.planes))) return st;
+  } else {
+    release(c->planes);
   }
   if (!cs.lights.dev.empty()) {
     if ((st = up(c->lights, cs.lights.dev))) return st;
@@ -637,6 +643,13 @@ int rt_scene_stats_get(rt_ctx* c, rt_scene_stats* out) {
   if (!c || !out) return RT_E_INVALID;
   if (!c->have_scene) return fail(c, RT_E_INVALID, "no scene uploaded");
   *out = c->stats;
+  return RT_OK;
+}
+
+int rt_scene_hop_instance(rt_ctx* c, int32_t* out) {
+  if (!c || !out) return RT_E_INVALID;
+  if (!c->have_scene) return fail(c, RT_E_INVALID, "no scene uploaded");
+  *out = hop_instance(c->place);
   return RT_OK;
 }
 
@@ -806,12 +819,12 @@ int rt_counters_get(rt_ctx* c, rt_counters* out) {
     double ph[kPhBuckets] = {};
     for (const DCounters& k : dc)
       for (int i = 0; i < kPhBuckets; ++i) ph[i] += (double)k.pad[i];
-    const int order[] = {kPhTrav, kPhRecord, kPhRegen, kPhMarble, kPhDraws, kPhCamera, kPhShade, kPhTail};
-    const char* names[] = {"trav", "record", "regen", "marble", "draws", "camera", "shade", "tail"};
+    const int order[] = {kPhTrav, kPhDown, kPhRecord, kPhRegen, kPhMarble, kPhDraws, kPhCamera, kPhShade, kPhTail, kPhHop};
+    const char* names[] = {"trav", "down", "record", "regen", "marble", "draws", "camera", "shade", "tail", "hop"};
     double tot = 0;
     for (int b : order) tot += ph[b];
     fprintf(stderr, "[phase] wave-time fractions:");
-    for (int i = 0; i < 8; ++i) fprintf(stderr, " %s %.4f", names[i], ph[order[i]] / tot);
+    for (int i = 0; i < 10; ++i) fprintf(stderr, " %s %.4f", names[i], ph[order[i]] / tot);
     fprintf(stderr, " (wave-cycles %.4g)\n", tot);
     const double lane = ph[kPhLaneSteps], wave = ph[kPhWaveSteps];
     fprintf(stderr, "[phase] traversal lane steps %.4g, wave steps %.4g, SIMD utilisation %.3f\n", lane, wave,

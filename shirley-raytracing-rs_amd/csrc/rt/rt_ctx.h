@@ -47,6 +47,7 @@ struct rt_ctx {
   rt::DScene scene{};
   DevBuf nodes, nodes4, prims, mats, texs, perlin, texels, exts;
   DevBuf ground;  // the ground-stack record and its guard bitmap (place.hop_kind == 2; rt_layout.h DGround)
+  DevBuf planes;  // the plane record of a plane stack (place.hop_planes; rt_layout.h DPlanes)
   // the scene's light list (rt_scene_lights): the public records, and their device copies (DLight) that
   // rt_render_direct hands to its kernel as an argument of its own
   DevBuf lights;

@@ -1063,10 +1063,13 @@ __device__ __forceinline__ int traverse(const DScene& S, const DNode* lds_nodes,
 // per-lane step counter of the instrumented build (a register of the calling kernel)
 #define g_trav_lane_steps trav_lane_steps_ref
 // event counters of the instrumented build: slot 2i += active lanes, slot 2i + 1 += 1 (per wave)
-constexpr int kPhaseEvents = 48;
+constexpr int kPhaseEvents = 52;
 static __device__ unsigned long long g_phase_ctr[2 * kPhaseEvents];
 // histograms of the instrumented build: node visits per traversing lane, and per wave (its slowest lane)
 static __device__ unsigned long long g_visit_hist[64], g_wave_visit_hist[64];
+// wave-cycles inside the runs of the hop passes, by part (kHopClk*; trace.hip PH_PART)
+enum : int { kHopClkDownServe = 0, kHopClkDownNext = 1, kHopClkHopNext = 2, kHopClkHopServe = 3, kHopClks = 4 };
+static __device__ unsigned long long g_hop_clk[kHopClks];
 
 __device__ __forceinline__ void ph_count(int i) {
   const unsigned long long act = __ballot(1);
@@ -1718,6 +1721,62 @@ __device__ __forceinline__ int ground_hop_t(const DScene& S, const DPrim* lds_pr
 __device__ __forceinline__ bool ground_hop(const DScene& S, const DPrim* lds_prims, const DMat* mats, GGround* g, v3 o, v3 d,
                                            double t_min, double& t_best, int& best, int& face_best, bool& guarded) {
   return ground_hop_t<false>(S, lds_prims, mats, g, o, d, t_min, t_best, best, face_best, guarded) != kHopRefused;
+}
+
+// ground_hop_t on a plane stack (rt_layout.h DPlanes, scene_compile.cpp plane_stack; trace.hip HOP = 4): the same
+// answer without the leaf machinery, or no answer.  Under ground_hop_t's origin, |d.y| and slope conditions a ray
+// whose origin and hit point lie inside the shrunk core meets, of all G, the next plane in its direction of travel
+// first: one wave-uniform walk over the sorted planes picks it — the first beyond o.y + tol going
+// up, the last below o.y - tol going down; a plane within tol of o.y is the one the ray stands on, its quotient
+// below t_min by dy_min — and t is the correctly rounded (y_k - o.y) / d.y, the quotient box_t1f / rect_t form
+// (face_div: |d.y| in [2^-100, 2^300] and |y_k - o.y| in [tol, 2^21] are in its range).  Answered when the list
+// has an answer for that plane, t > 2 t_min, the hit record's own point o + t d lies inside the shrunk core and,
+// leaving through Y, its guard cell is free; DOWN as in ground_hop_t.  kHopRefused: the lane declines — the outputs
+// mean nothing and it traverses as before.
+typedef __attribute__((address_space(4))) const DPlanes GPlanes;
+template <bool DOWN>
+__device__ __forceinline__ int plane_hop_t(GGround* g, GPlanes* pl, v3 o, v3 d, double t_min, double& t_best, int& best,
+                                           int& face_best, bool& guarded) {
+  guarded = false;
+  const double ay = fabs(d.y);
+  const double x0 = pl->x0, x1 = pl->x1, z0 = pl->z0, z1 = pl->z1;
+  const bool slab_ok = o.y >= g->y_lo && o.y <= g->y_hi && ay >= g->dy_min && ay <= 0x1p300 &&
+                       d.x * d.x + d.z * d.z <= g->ratio2 * (d.y * d.y);
+  if (!(slab_ok && o.x >= x0 && o.x <= x1 && o.z >= z0 && o.z <= z1)) return kHopRefused;
+  const bool up = d.y > 0.0;
+  const double tol = pl->tol, hi = o.y + tol, lo = o.y - tol;
+  double y = 0.0;
+  int info = -1;
+  const int n = pl->n;
+#pragma unroll 1
+  for (int k = 0; k < n; ++k) {
+    const double yk = pl->y[k];
+    const bool take = up ? (yk > hi && info < 0) : yk < lo;
+    y = take ? yk : y;
+    info = take ? pl->info[k] : info;
+  }
+  const int kind = info < 0 ? kHopRefused : ((info >> 2) & 3);
+  if (kind == kHopRefused || (!DOWN && kind != kHopServed)) return kHopRefused;
+  const double t = div_recip(y - o.y, Recip{d.y, div_recip(1.0, recip(d.y))});
+  if (!(t > 2.0 * t_min)) return kHopRefused;
+  const double hx = o.x + t * d.x, hz = o.z + t * d.z;
+  if (!(hx >= x0 && hx <= x1 && hz >= z0 && hz <= z1)) return kHopRefused;
+  if ((info & 16) && kind == kHopServed) {
+    // leaving through Y: the exit point's cell, as in ground_hop_t
+    const int nx = g->nx;
+    const int ix = ground_cell(hx, g->x0, nx), iz = ground_cell(hz, g->z0, g->nz);
+    if (ix >= 0 && iz >= 0) {
+      typedef __attribute__((address_space(1))) const uint32_t GBits;
+      const unsigned c = (unsigned)iz * (unsigned)nx + (unsigned)ix;
+      GBits* bits = (GBits*)(uintptr_t)((uint64_t)(uintptr_t)g + sizeof(DGround));
+      guarded = (bits[c >> 5] >> (c & 31u)) & 1u;
+      if (guarded) return kHopRefused;
+    }
+  }
+  t_best = t;
+  best = (int)((unsigned)info >> 5);
+  face_best = (info & 3) == 0 ? -1 : 3 + (info & 3);
+  return kind;
 }
 
 // Step-wise form for wf_extend4, where a ray's traversal state lives across loop iterations.

@@ -229,6 +229,24 @@ RT_HOST_DEVICE inline int ground_cell(double v, double v0, int n) {
   return (q >= 0.0 && q < (double)n) ? (int)q : -1;
 }
 
+// The plane record of a ground stack that is a *plane stack* (scene_compile.cpp plane_stack): every
+// y plane of G — a rect's own, both faces of a RectBox — in ascending order, no two within `gap` of each other, and
+// the rectangle every primitive's xz extent contains, shrunk by the margin mx.  A ray inside the slab that keeps
+// origin and hit point inside that core meets the next plane in its direction of travel first (rt_device.h
+// plane_hop_t, the HOP = 4 instances).  info: bits 0-1 the face (0 a rect, 1 / 2 a RectBox's face 4 / 5), bits 2-3
+// the answer (kHopRefused: never — a dielectric rect, another material's plane above Y - gap; kHopServed: a
+// dielectric RectBox face; kHopFound: another material's plane at or below Y - gap), bit 4 the plane is Y itself,
+// bits 5 up the primitive.
+constexpr int kGroundMaxPlanes = 2 * kGroundMaxPrims;
+struct alignas(16) DPlanes {
+  double x0, x1, z0, z1;  // the core, shrunk
+  double tol;             // a plane within tol of o.y is the one the ray stands on
+  int32_t n, pad;
+  double y[kGroundMaxPlanes];
+  int32_t info[kGroundMaxPlanes];
+};
+static_assert(sizeof(DPlanes) == 144, "DPlanes layout");
+
 struct DCamera {
   int32_t width, height;   // image dims
   int32_t has_lens;
@@ -297,8 +315,12 @@ constexpr int kCounterSlots = 64;
 // traversal step statistics
 enum : int {
   kPhRegen = 0, kPhTrav = 1, kPhShade = 2, kPhLaneSteps = 3, kPhWaveSteps = 4, kPhRecord = 5, kPhMarble = 6,
-  kPhDraws = 7, kPhCamera = 8, kPhTail = 9, kPhBuckets = 10
+  kPhDraws = 7, kPhCamera = 8, kPhTail = 9,
+  kPhDown = 10,  // the down pass (trace.hip step 1'), apart from the traversal before it
+  kPhHop = 11,   // the hop pass (steps 5 / 5'), apart from the tail before it
+  kPhBuckets = 12
 };
+static_assert(kPhBuckets <= (int)(sizeof(DCounters::pad) / sizeof(unsigned long long)), "DCounters.pad slots");
 
 struct KParams {
   DScene scene;
@@ -325,6 +347,7 @@ struct alignas(16) KBlock {
   unsigned long long* unit_counter;
   DCounters* counters;
   const DGround* ground;  // the scene's ground stack (the HOP = 2 instances only; else null)
+  const DPlanes* planes;  // ... and its plane record (the HOP = 4 instances only; else null)
 };
 
 // ---- wavefront engine (wavefront.hip): path state of P slots as structure-of-arrays in HBM ----

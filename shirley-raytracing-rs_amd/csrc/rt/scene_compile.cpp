@@ -40,6 +40,7 @@ SceneTuning tuning_from_env() {
   if (const char* e = getenv("SHIRLEY_HOP")) {
     t.hop_root = std::strcmp(e, "root") == 0;
     t.hop_up = std::strcmp(e, "up") == 0;
+    t.hop_general = std::strcmp(e, "general") == 0;
   }
   if (const char* e = getenv("SHIRLEY_SAH_BOXW")) t.sah_box_weight = atof(e);
   t.sah_binned = getenv("SHIRLEY_SAH_BINNED") != nullptr;
@@ -590,7 +591,11 @@ namespace {
 // ends with t1 <= t0 on that axis for every ray with a finite non-zero d.y, so the reference never tests the
 // sphere for such a ray (random_scene holds two: check_fit_ball shrinks a ball below zero where it overlaps).
 bool sphere_never_hit(const double* p) { return p[3] <= 0.0 && p[1] - p[3] >= p[1] + p[3]; }
-bool ground_stack(const std::vector<DPrim>& prims, int n_prims, std::vector<uint32_t>& out) {
+// (the proof's constants that plane_stack below builds on: gap, tol, reach and B, the largest |x|, |z| of G's extent)
+struct GroundConsts {
+  double gap = 0.0, tol = 0.0, reach = 0.0, ext = 0.0;
+};
+bool ground_stack(const std::vector<DPrim>& prims, int n_prims, std::vector<uint32_t>& out, GroundConsts* consts = nullptr) {
   out.clear();
   std::vector<int32_t> boxes, rects;
   double top = -std::numeric_limits<double>::infinity(), low = -top;
@@ -651,6 +656,12 @@ bool ground_stack(const std::vector<DPrim>& prims, int n_prims, std::vector<uint
   const double gap = 4.0 * eta + 4.0 * tol;
   for (double y : planes)
     if (y != top && !(y <= top - gap)) return false;
+  if (consts) {
+    consts->gap = gap;
+    consts->tol = tol;
+    consts->reach = reach;
+    consts->ext = std::max(std::max(std::fabs(ex0), std::fabs(ex1)), std::max(std::fabs(ez0), std::fabs(ez1)));
+  }
 
   DGround g;
   std::memset(&g, 0, sizeof g);
@@ -701,6 +712,66 @@ bool ground_stack(const std::vector<DPrim>& prims, int n_prims, std::vector<uint
         }
       }
   }
+  return true;
+}
+
+// Is the ground stack `ground` (ground_stack's record) a plane stack (rt_layout.h DPlanes; the proof: DESIGN.md
+// §3.1)?  Exact binary64 compares on the values the reference's leaf boxes hold, like ground_stack's:
+//   * no two y planes of G — a rect's own plane, both faces of a RectBox — within `gap` of each other;
+//   * the rectangle common to every primitive's xz extent, shrunk by mx on each side, is not empty and contains the
+//     guard bitmap's rectangle.
+// mx = 2^-44 (B + reach + 1): 2^4 times the 2^-48 (B + L) of sphere_t_sure's eta, with the longest served segment's
+// horizontal run for L — far above the 3 * 2^-53 (B + reach) a hit point o + t d is off by, and above the
+// 2^-50 (B + reach) that keeps a side plane's quotient and slab product strictly behind the hit's.
+bool plane_stack(const std::vector<DPrim>& prims, const std::vector<DMat>& mats, const std::vector<uint32_t>& ground,
+                 const GroundConsts& k, std::vector<uint32_t>& out) {
+  out.clear();
+  DGround g;
+  std::memcpy(&g, ground.data(), sizeof g);
+  const double inf = std::numeric_limits<double>::infinity();
+  double x0 = -inf, x1 = inf, z0 = -inf, z1 = inf;
+  struct Plane {
+    double y;
+    int32_t info;
+  };
+  std::vector<Plane> pl;
+  // (the answers: rt_device.h kHopRefused 0, kHopServed 1, kHopFound 2; a rect counts by the top of its padded box
+  // for y_down, as ground_hop_t does)
+  auto info = [](int32_t prim, int face, int answer, bool top) {
+    return (int32_t)((uint32_t)prim << 5 | (top ? 16u : 0u) | (uint32_t)answer << 2 | (face < 0 ? 0u : (face == 4 ? 1u : 2u)));
+  };
+  for (int i = 0; i < g.n; ++i) {
+    const int32_t leaf = g.prim[i];
+    if (leaf < 0 || leaf >= (1 << 26)) return false;
+    const DPrim& q = prims[leaf];
+    const double* p = q.p;
+    const bool diel = mats[q.material].kind == RT_MAT_DIELECTRIC;
+    if (i < g.n_box) {
+      x0 = std::max(x0, p[0]), x1 = std::min(x1, p[3]), z0 = std::max(z0, p[2]), z1 = std::min(z1, p[5]);
+      for (int face = 4; face <= 5; ++face) {
+        const double y = face == 4 ? p[4] : p[1];
+        pl.push_back({y, info(leaf, face, diel ? 1 : (y <= g.y_down ? 2 : 0), y == g.y_top)});
+      }
+    } else {
+      x0 = std::max(x0, p[0]), x1 = std::min(x1, p[1]), z0 = std::max(z0, p[2]), z1 = std::min(z1, p[3]);
+      pl.push_back({p[4], info(leaf, -1, (!diel && p[4] + 0.0001 <= g.y_down) ? 2 : 0, false)});
+    }
+  }
+  std::stable_sort(pl.begin(), pl.end(), [](const Plane& a, const Plane& b) { return a.y < b.y; });
+  for (size_t i = 1; i < pl.size(); ++i)
+    if (!(pl[i].y - pl[i - 1].y > k.gap)) return false;
+  const double mx = 0x1p-44 * (k.ext + k.reach + 1.0);
+  DPlanes d;
+  std::memset(&d, 0, sizeof d);
+  d.x0 = x0 + mx, d.x1 = x1 - mx, d.z0 = z0 + mx, d.z1 = z1 - mx;
+  if (!(d.x0 < d.x1 && d.z0 < d.z1)) return false;
+  if (g.nx > 0 && !(g.x0 >= d.x0 && g.x0 + g.nx * kGroundCell <= d.x1 && g.z0 >= d.z0 && g.z0 + g.nz * kGroundCell <= d.z1))
+    return false;
+  d.tol = k.tol;
+  d.n = (int32_t)pl.size();
+  for (size_t i = 0; i < pl.size(); ++i) d.y[i] = pl[i].y, d.info[i] = pl[i].info;
+  out.assign(sizeof(DPlanes) / 4, 0u);
+  std::memcpy(out.data(), &d, sizeof d);
   return true;
 }
 
@@ -778,7 +849,8 @@ int plan_placement(const rt_scene_desc* d, int32_t placement, const SceneTuning&
   }
   P.hop_pass = coat && !ext && prims_lds && !tune.no_hop;  // tuning
   // ... by the scene's ground stack where it has one (SHIRLEY_HOP=root: never), else by a first-node visit
-  P.hop_kind = !P.hop_pass ? 0 : (!tune.hop_root && ground_stack(cs.prims, d->n_objects, cs.ground)) ? 2 : 1;
+  GroundConsts consts;
+  P.hop_kind = !P.hop_pass ? 0 : (!tune.hop_root && ground_stack(cs.prims, d->n_objects, cs.ground, &consts)) ? 2 : 1;
   if (P.hop_kind != 2) cs.ground.clear();
   // ... and, before the sampler, the downward hops too (trace.hip, HOP = 3) where the stack holds a primitive the
   // down pass can find: one of another material on a plane at least `gap` below Y (SHIRLEY_HOP=up: never)
@@ -793,6 +865,10 @@ int plan_placement(const rt_scene_desc* d, int32_t placement, const SceneTuning&
       P.hop_down = i < g.n_box ? (q.p[1] <= g.y_down || q.p[4] <= g.y_down) : q.p[4] + 0.0001 <= g.y_down;
     }
   }
+  // ... both by the closed-form next plane (trace.hip, HOP = 4) where the stack is a plane stack (SHIRLEY_HOP=general:
+  // never); a stack that misses a premise keeps the general passes
+  P.hop_planes = P.hop_down && !tune.hop_general && plane_stack(cs.prims, cs.mats, cs.ground, consts, cs.planes);
+  if (!P.hop_planes) cs.planes.clear();
 
   // wavefront extend block: its own (larger) stack area, the rest of LDS for nodes
   const long long wf_stack = (long long)wf_extend_lds(0, P.stack_depth);

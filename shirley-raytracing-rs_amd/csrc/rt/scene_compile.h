@@ -33,6 +33,7 @@ struct SceneTuning {
   bool no_hop = false;          // SHIRLEY_NO_HOP
   bool hop_root = false;        // SHIRLEY_HOP=root: the first-node hop pass where the ground-stack one would run
   bool hop_up = false;          // SHIRLEY_HOP=up: the ground-stack pass without its down pass (ScenePlacement.hop_down)
+  bool hop_general = false;     // SHIRLEY_HOP=general: a plane stack keeps the general passes (ScenePlacement.hop_planes)
   double sah_box_weight = 4.0;  // SHIRLEY_SAH_BOXW=<c>
   bool sah_binned = false;      // SHIRLEY_SAH_BINNED
   bool wf_extend2 = false;      // SHIRLEY_WF_EXTEND2
@@ -59,11 +60,14 @@ struct ScenePlacement {
   bool hop_pass = false;        // the megakernel runs its instances with the hop pass (trace.hip)
   int hop_kind = 0;             // ... of which kind (rt_scene_stats.hop_kind): 1 first-node visit, 2 ground stack
   bool hop_down = false;        // hop_kind 2 with the down pass before the sampler (trace.hip, HOP = 3)
+  bool hop_planes = false;      // hop_down on a plane stack: both passes by the closed-form next plane (HOP = 4)
 };
 
-// The megakernel's HOP instance of a placement (rt_launch.h launch_trace, trace_occupancy): hop_kind, or 3 for the
-// ground-stack pass with the down pass.
-inline int hop_instance(const ScenePlacement& P) { return P.hop_kind == 2 && P.hop_down ? 3 : P.hop_kind; }
+// The megakernel's HOP instance of a placement (rt_launch.h launch_trace, trace_occupancy; rt_scene_hop_instance):
+// hop_kind, or 3 for the ground-stack pass with the down pass, or 4 for the two on a plane stack.
+inline int hop_instance(const ScenePlacement& P) {
+  return P.hop_kind == 2 && P.hop_down ? (P.hop_planes ? 4 : 3) : P.hop_kind;
+}
 
 // The plan's fields of the megakernel's device scene record.
 inline void place_scene(const ScenePlacement& P, DScene& S) {
@@ -117,6 +121,8 @@ struct CompiledScene {
   std::vector<size_t> img_off;
   // hop_kind 2: the ground-stack record followed by its guard bitmap (rt_layout.h DGround); else empty
   std::vector<uint32_t> ground;
+  // hop_planes: the stack's plane record (rt_layout.h DPlanes); else empty
+  std::vector<uint32_t> planes;
   // device primitive number -> object index (primitives are numbered in the reference tree's leaf order)
   std::vector<int32_t> prim_object;
   // flattened rotated spheres (flat_object): object index -> RotateY's cos, sin, for rt_scene_hit's u, v

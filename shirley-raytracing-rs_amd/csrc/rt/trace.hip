@@ -62,7 +62,8 @@ constexpr int kNarrowWaves = RT_NARROW_WAVES;
 // that every other call runs the code it ran without the list.
 // HOP: the hop pass at the end of the iteration body (below) — 0: none; 1: by a visit of the tree's first node;
 // 2: from the scene's ground stack (ScenePlacement.hop_kind); 3: the same with the down pass after the traversal
-// (ScenePlacement.hop_down) — compiled only into the scene-in-LDS
+// (ScenePlacement.hop_down); 4: 3 on a plane stack, both passes by the closed-form next plane
+// (ScenePlacement.hop_planes) — compiled only into the scene-in-LDS
 // reference-scene instances that launch_trace picks for a scene with a dielectric RectBox (ScenePlacement.hop_pass),
 // so every other instance keeps its code.
 #ifndef RT_HOP_MIN_LANES
@@ -103,6 +104,24 @@ constexpr int kNarrowWaves = RT_NARROW_WAVES;
 #endif
 #ifndef RT_HOP3_MIN_LANES_B
 #define RT_HOP3_MIN_LANES_B RT_HOP2_MIN_LANES_B
+#endif
+// HOP = 4 (HOP = 3 on a plane stack, ScenePlacement.hop_planes): the same two passes with plane_hop_t for the stack's
+// answer — no general ground_hop_t code in the instance.  Its own thresholds, re-swept with the cheaper run: the down
+// pass at 24 / 16 / 16 and step 5' at 16 / 8 (profiles/planehop/threshold_sweep.jsonl).
+#ifndef RT_HOP4D_MIN_LANES_A
+#define RT_HOP4D_MIN_LANES_A 24
+#endif
+#ifndef RT_HOP4D_MIN_LANES_B
+#define RT_HOP4D_MIN_LANES_B RT_HOPD_MIN_LANES_B
+#endif
+#ifndef RT_HOP4D_MIN_LANES_C
+#define RT_HOP4D_MIN_LANES_C RT_HOPD_MIN_LANES_C
+#endif
+#ifndef RT_HOP4_MIN_LANES_A
+#define RT_HOP4_MIN_LANES_A 16
+#endif
+#ifndef RT_HOP4_MIN_LANES_B
+#define RT_HOP4_MIN_LANES_B 8
 #endif
 #ifdef RT_HOP_SERVE_SHARED
 // A/B only: the serve body of the HOP = 3 instances as one call that the down pass and step 5' both
@@ -195,9 +214,25 @@ void trace_kernel(KParams P) {
     ph_t[b] += ph_now - ph_last;                  \
     ph_last = ph_now;                             \
   } while (0)
+  // ... and, inside a run of the hop passes, the wave's cycles by part (serve body / next hit with its guard read):
+  // begun and added by the same set of lanes, one of which adds the wave's cycles to g_hop_clk
+  unsigned long long ph_part_last = 0;
+#define PH_PART_BEGIN() ph_part_last = clock64()
+#define PH_PART(b)                                                                                                \
+  do {                                                                                                            \
+    const unsigned long long ph_now = clock64();                                                                  \
+    if ((int)__lane_id() == __builtin_ctzll(__ballot(1))) atomicAdd(&g_hop_clk[b], ph_now - ph_part_last);        \
+    ph_part_last = ph_now;                                                                                        \
+  } while (0)
 #else
 #define PH_STAMP(b) \
   do {              \
+  } while (0)
+#define PH_PART_BEGIN() \
+  do {                  \
+  } while (0)
+#define PH_PART(b) \
+  do {             \
   } while (0)
 #endif
 #ifdef RT_TIMELINE
@@ -231,9 +266,9 @@ void trace_kernel(KParams P) {
     h.front_face = false;
     PH_COUNT(6);
     n_seg += __popcll(__ballot(active));
-    // 1'. the down pass (HOP = 3).  A lane whose traversal hit is a dielectric primitive of the
+    // 1'. the down pass (HOP = 3, 4).  A lane whose traversal hit is a dielectric primitive of the
     // ground stack — the coat's top from above, mostly — is shaded here by the hop pass's serve body and asks the
-    // stack for its next hit (ground_hop_t<true>): a dielectric one, served, sends it round again (up to three
+    // stack for its next hit (ground_hop_t<true>; HOP = 4: plane_hop_t<true>): a dielectric one, served, sends it round again (up to three
     // runs, each with its own lane threshold); any other one that the stack's conditions prove the scene's closest —
     // the rect under the coat — becomes the lane's hit of this iteration, recorded, sampled and shaded by the
     // ordinary steps below; step 5 then takes the lane up through the coat.  One ground interaction is one
@@ -242,7 +277,7 @@ void trace_kernel(KParams P) {
     // same functions of (seed, pixel, sample, draw index, ray) in each lane's own order as the iterations it
     // replaces: frames and counters are bit-identical with and without the pass.
     bool waiting = false;
-    if constexpr (HOP == 3) {
+    if constexpr (HOP >= 3) {
       static_assert(MODE == kSceneLds && !EXT, "the hop pass is built for the scene-in-LDS reference-scene instances");
       // (the pass's ballots need a wave-uniform point: this instance traverses here, not in the block below)
       if (active)
@@ -259,11 +294,13 @@ void trace_kernel(KParams P) {
 #pragma unroll 1
       for (int run = 0; run < 3; ++run) {
         if (__popcll(__ballot(pend)) <
-            (run == 0 ? RT_HOPD_MIN_LANES_A : (run == 1 ? RT_HOPD_MIN_LANES_B : RT_HOPD_MIN_LANES_C)))
+            (HOP == 4 ? (run == 0 ? RT_HOP4D_MIN_LANES_A : (run == 1 ? RT_HOP4D_MIN_LANES_B : RT_HOP4D_MIN_LANES_C))
+                      : (run == 0 ? RT_HOPD_MIN_LANES_A : (run == 1 ? RT_HOPD_MIN_LANES_B : RT_HOPD_MIN_LANES_C))))
           break;
         int kind = kHopRefused;
         if (pend) {
           PH_COUNT(36 + 4 * run);
+          PH_PART_BEGIN();
           pend = false;
 #ifdef RT_HOP_SERVE_SHARED
           const ServeOut so = hop_serve_ool(lds_prims, mats, prim, face, o, d, t_best, rng, seed);
@@ -283,13 +320,18 @@ void trace_kernel(KParams P) {
           // (who tries: a ray that runs on inside the box it hit, as in step 5', or downwards out of it, towards
           // what lies under it in the stack; one that left upwards meets the spheres or the sky, and waits)
           const bool inward = face < 0 || d.y < 0.0 || box_inward(face, d);
+          PH_PART(kHopClkDownServe);
           prim = -1;
           waiting = active;
           if (active && inward) {
+            PH_COUNT(48 + run);  // (asks the stack: served + found answered, the rest declined or refused)
             double t_hop;
             int p_hop, f_hop;
             bool guarded;
-            kind = ground_hop_t<true>(S, lds_prims, mats, g, o, d, 0.001, t_hop, p_hop, f_hop, guarded);
+            if constexpr (HOP == 4)
+              kind = plane_hop_t<true>(g, (GPlanes*)kblock(P.kconst)->planes, o, d, 0.001, t_hop, p_hop, f_hop, guarded);
+            else
+              kind = ground_hop_t<true>(S, lds_prims, mats, g, o, d, 0.001, t_hop, p_hop, f_hop, guarded);
             if (kind != kHopRefused) {
               prim = p_hop;
               face = f_hop;
@@ -299,14 +341,15 @@ void trace_kernel(KParams P) {
               if (pend) PH_COUNT(37 + 4 * run); else PH_COUNT(38 + 4 * run);
             }
           }
+          PH_PART(kHopClkDownNext);
           if (waiting) PH_COUNT(39 + 4 * run);
         }
         n_seg += __popcll(__ballot(kind != kHopRefused));
       }
-      PH_STAMP(kPhTrav);
+      PH_STAMP(kPhDown);
     }
     if (active) {
-      if constexpr (HOP != 3)
+      if constexpr (HOP < 3)
         prim = traverse4<THREADS, MODE, EXT>(S, lds_nodes, lds_prims, o, d, 0.001, t_best, face, stk, rng, seed, visits,
                                         ptests RT_STAT_ARG(ph_lane_steps));
 #ifdef RT_PHASE_TIMING
@@ -592,15 +635,16 @@ void trace_kernel(KParams P) {
           }
         }
       }
-      PH_STAMP(kPhTail);
+      PH_STAMP(kPhHop);
     }
-    // 5'. the hop pass of a scene with a ground stack (HOP = 2; rt_device.h ground_hop): the same
+    // 5'. the hop pass of a scene with a ground stack (HOP = 2, 3; rt_device.h ground_hop; HOP = 4: plane_hop_t<false>,
+    // which declines where ground_hop would refuse, and where it cannot tell): the same
     // candidates, but the closest hit comes from the stack's own primitives — at most four, no node visit — and
     // is served where the stack's conditions prove it the scene's closest hit.  That also decides the upward
     // hop inside the coat, which no first-node visit can (the spheres' boxes start on the coat's top plane), so
     // the pass runs twice: the second run's candidates are the lanes the first one served, which turns "coat
     // bottom from below, coat top from inside" into one iteration.  Each run has its own lane threshold.
-    if constexpr (HOP == 2 || HOP == 3) {
+    if constexpr (HOP >= 2) {
       static_assert(MODE == kSceneLds && !EXT, "the hop pass is built for the scene-in-LDS reference-scene instances");
       bool cand = active && !regen && hit;
       if (cand) cand = lds_prims[prim].kind != kPrimSphere;
@@ -613,21 +657,29 @@ void trace_kernel(KParams P) {
 #endif
 #pragma unroll 1
       for (int run = 0; run < 2; ++run) {
-        if (__popcll(__ballot(cand)) < (HOP == 3 ? (run ? RT_HOP3_MIN_LANES_B : RT_HOP3_MIN_LANES_A)
-                                                 : (run ? RT_HOP2_MIN_LANES_B : RT_HOP2_MIN_LANES_A)))
+        if (__popcll(__ballot(cand)) < (HOP == 4   ? (run ? RT_HOP4_MIN_LANES_B : RT_HOP4_MIN_LANES_A)
+                                        : HOP == 3 ? (run ? RT_HOP3_MIN_LANES_B : RT_HOP3_MIN_LANES_A)
+                                                   : (run ? RT_HOP2_MIN_LANES_B : RT_HOP2_MIN_LANES_A)))
           break;
         bool serve = false;
         double t_hop = __builtin_inf();
         int p_hop = -1, f_hop = -1;
         if (cand) {
           if (run) PH_COUNT(28); else PH_COUNT(26);
+          PH_PART_BEGIN();
           bool guarded;
-          serve = ground_hop(S, lds_prims, mats, (GGround*)kblock(P.kconst)->ground, o, d, 0.001, t_hop, p_hop, f_hop, guarded);
+          if constexpr (HOP == 4)
+            serve = plane_hop_t<false>((GGround*)kblock(P.kconst)->ground, (GPlanes*)kblock(P.kconst)->planes, o, d, 0.001, t_hop,
+                                       p_hop, f_hop, guarded) != kHopRefused;
+          else
+            serve = ground_hop(S, lds_prims, mats, (GGround*)kblock(P.kconst)->ground, o, d, 0.001, t_hop, p_hop, f_hop, guarded);
+          PH_PART(kHopClkHopNext);
           if (guarded) PH_COUNT(30);
         }
         n_seg += __popcll(__ballot(serve));
         if (serve) {
           if (run) PH_COUNT(29); else PH_COUNT(27);
+          PH_PART_BEGIN();
 #ifdef RT_HOP_SERVE_SHARED
           if constexpr (HOP == 3) {
             const ServeOut so = hop_serve_ool(lds_prims, mats, p_hop, f_hop, o, d, t_hop, rng, seed);
@@ -646,13 +698,14 @@ void trace_kernel(KParams P) {
             sum = sum + em;
             active = false;  // takes its next sample in the next iteration's step 2
           }
+          PH_PART(kHopClkHopServe);
         }
         cand = serve && active;
 #if RT_HOP2_INSIDE
         if (cand) cand = box_inward(f_hop, d);
 #endif
       }
-      PH_STAMP(kPhTail);
+      PH_STAMP(kPhHop);
     }
 #ifdef RT_TIMELINE
     if (exhausted && !ph_exh_seen) {
@@ -1116,6 +1169,7 @@ hipError_t trace_occupancy(const DScene& S, int threads, int hop, int* blocks_pe
   if (hop && !(threads == kTraceThreadsWide && !S.exts && S.n_lds_prims > 0)) return hipErrorInvalidValue;
   if (threads == kTraceThreadsWide && !S.exts) {  // reference scenes only: book-2 scenes take kTraceThreadsWide3
     if (node_mode4(S) != kNodesLds) return hipErrorInvalidValue;
+    if (hop == 4) return occupancy_impl1<kTraceThreadsWide, kSceneLds, false, 4>(S, blocks_per_cu);
     if (hop == 3) return occupancy_impl1<kTraceThreadsWide, kSceneLds, false, 3>(S, blocks_per_cu);
     if (hop == 2) return occupancy_impl1<kTraceThreadsWide, kSceneLds, false, 2>(S, blocks_per_cu);
     if (hop) return occupancy_impl1<kTraceThreadsWide, kSceneLds, false, 1>(S, blocks_per_cu);
@@ -1139,7 +1193,9 @@ hipError_t launch_trace(const KParams& p, int blocks, int threads, int hop, hipS
                                      p.scene.n_lds_mats, p.scene.n_lds_texs);
   if (hop && !(threads == kTraceThreadsWide && !p.scene.exts && p.scene.n_lds_prims > 0)) return hipErrorInvalidValue;
   if (threads == kTraceThreadsWide && !p.scene.exts) {
-    if (hop == 3)
+    if (hop == 4)
+      launch_trace2<kTraceThreadsWide, kSceneLds, false, 4>(p, blocks, lds, stream);
+    else if (hop == 3)
       launch_trace2<kTraceThreadsWide, kSceneLds, false, 3>(p, blocks, lds, stream);
     else if (hop == 2)
       launch_trace2<kTraceThreadsWide, kSceneLds, false, 2>(p, blocks, lds, stream);
@@ -1308,7 +1364,10 @@ void phase_counters_dump() {
                                 // the down pass (HOP = 3), per run: lanes tried, served, found, left waiting
                                 "down1_try", "down1_served", "down1_found", "down1_wait",
                                 "down2_try", "down2_served", "down2_found", "down2_wait",
-                                "down3_try", "down3_served", "down3_found", "down3_wait"};
+                                "down3_try", "down3_served", "down3_found", "down3_wait",
+                                // ... and the lanes of each run that ask the stack (alive, running inward or down):
+                                // ask - served - found were refused (HOP = 4: declined)
+                                "down1_ask", "down2_ask", "down3_ask"};
   static_assert(sizeof names / sizeof names[0] <= kPhaseEvents, "event slots");
   for (int i = 0; i < (int)(sizeof names / sizeof names[0]); ++i)
     if (h[2 * i + 1])
@@ -1320,6 +1379,21 @@ void phase_counters_dump() {
     fprintf(stderr, "[phase-hist] visits: lanes / waves (slowest lane)\n");
     for (int i = 1; i < 64; ++i)
       if (lh[i] || wh[i]) fprintf(stderr, "[phase-hist] %2d %.6g %.6g\n", i, (double)lh[i], (double)wh[i]);
+  }
+  unsigned long long hc[kHopClks];
+  if (hipMemcpyFromSymbol(hc, HIP_SYMBOL(g_hop_clk), sizeof hc) == hipSuccess) {
+    // (per run: the waves of down1_try + down2_try + down3_try, hop_candidate + hop2_candidate, hop_served + hop2_served)
+    const double down_runs = (double)(h[2 * 36 + 1] + h[2 * 40 + 1] + h[2 * 44 + 1]);
+    const double hop_runs = (double)(h[2 * 26 + 1] + h[2 * 28 + 1]), hop_serves = (double)(h[2 * 27 + 1] + h[2 * 29 + 1]);
+    fprintf(stderr, "[phase-run] down pass: runs %.4g, wave-cycles per run: serve body %.1f, next hit (+ guard) %.1f\n", down_runs,
+            down_runs ? (double)hc[kHopClkDownServe] / down_runs : 0.0, down_runs ? (double)hc[kHopClkDownNext] / down_runs : 0.0);
+    fprintf(stderr, "[phase-run] hop pass: runs %.4g, wave-cycles per run: next hit (+ guard) %.1f; serving runs %.4g, serve body %.1f\n",
+            hop_runs, hop_runs ? (double)hc[kHopClkHopNext] / hop_runs : 0.0, hop_serves,
+            hop_serves ? (double)hc[kHopClkHopServe] / hop_serves : 0.0);
+    fprintf(stderr, "[phase-run] wave-cycles in all: down serve %.4g, down next %.4g, hop next %.4g, hop serve %.4g\n", (double)hc[0],
+            (double)hc[1], (double)hc[2], (double)hc[3]);
+    unsigned long long zc[kHopClks] = {};
+    (void)hipMemcpyToSymbol(HIP_SYMBOL(g_hop_clk), zc, sizeof zc);
   }
   unsigned long long z[2 * kPhaseEvents] = {};
   (void)hipMemcpyToSymbol(HIP_SYMBOL(g_phase_ctr), z, sizeof z);

@@ -167,6 +167,7 @@ RT_SIGNATURES = {
     "rt_last_error": (C.c_char_p, [C.c_void_p]),
     "rt_scene_upload": (C.c_int, [C.c_void_p, C.POINTER(rt_scene_desc), C.c_int32]),
     "rt_scene_stats_get": (C.c_int, [C.c_void_p, C.POINTER(rt_scene_stats)]),
+    "rt_scene_hop_instance": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     "rt_scene_digest": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "rt_scene_digest_host": (C.c_int, [C.POINTER(rt_scene_desc), C.c_int32, C.POINTER(C.c_uint64)]),
     "rt_render": (C.c_int, [C.c_void_p, C.POINTER(rt_camera), C.POINTER(rt_render_params), C.c_void_p]),

@@ -174,6 +174,12 @@ class Device:
         _check(self._h, N.rt_lib().rt_scene_stats_get(self._h, C.byref(s)))
         return s
 
+    def hop_instance(self) -> int:
+        """rt_scene_hop_instance: the megakernel instance of the uploaded scene's hop pass (0 .. 4)."""
+        k = C.c_int32()
+        _check(self._h, N.rt_lib().rt_scene_hop_instance(self._h, C.byref(k)))
+        return k.value
+
     def render(self, camera: N.rt_camera, settings: RenderSettings) -> np.ndarray:
         """Whole frame -> [H][W][3] f64 per-pixel sums, row 0 = bottom (Image.data layout)."""
         out = np.zeros((camera.image_height, camera.image_width, 3), dtype=np.float64)

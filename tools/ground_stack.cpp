@@ -5,7 +5,9 @@
 //   ground_stack <case>[/KEY=VALUE[,KEY=VALUE...]] ...
 //     case       a builtin of sh_scene_builtin (random, cornell, ...) or @<file>: a scene saved as JSON
 //     KEY=VALUE  the upload-time tuning variable SHIRLEY_<KEY>, set for this case only
-// prints one JSON line per case; `hop_down`: the launches take the down pass's instances (ScenePlacement.hop_down).
+// prints one JSON line per case; `hop_down`: the launches take the down pass's instances (ScenePlacement.hop_down);
+// `hop_planes`, `hop_instance`: ... those of a plane stack (ScenePlacement.hop_planes), with its record (rt_layout.h
+// DPlanes): `planes` the sorted y values as hex floats, `plane_info` their packed words, `core` the shrunk core and `tol`.
 // Guard check: every cell against the distance from its rectangle to the nearest contact point over all spheres
 // (`cells_wrong`), and 256 points on and inside the guard circle of every guarded sphere, which must all fall in
 // marked cells (`points_free`).
@@ -59,8 +61,18 @@ int main(int argc, char** argv) {
     std::string err;
     const int st = rt::compile_scene(sh_desc_view(desc), RT_BVH_SAH, tune, &cs, &err);
     std::printf("{\"case\": \"%s\", \"status\": %d, \"hop_pass\": %d, \"hop_kind\": %d, \"stats_hop_kind\": %d, "
-                "\"hop_down\": %d", argv[a], st, cs.place.hop_pass ? 1 : 0, cs.place.hop_kind, (int)cs.stats.hop_kind,
-                cs.place.hop_down ? 1 : 0);
+                "\"hop_down\": %d, \"hop_planes\": %d, \"hop_instance\": %d", argv[a], st, cs.place.hop_pass ? 1 : 0,
+                cs.place.hop_kind, (int)cs.stats.hop_kind, cs.place.hop_down ? 1 : 0, cs.place.hop_planes ? 1 : 0,
+                rt::hop_instance(cs.place));
+    if (st == 0 && cs.place.hop_planes) {
+      rt::DPlanes pl;
+      std::memcpy(&pl, cs.planes.data(), sizeof pl);
+      std::printf(", \"planes\": [");
+      for (int k = 0; k < pl.n; ++k) std::printf("%s\"%a\"", k ? ", " : "", pl.y[k]);
+      std::printf("], \"plane_info\": [");
+      for (int k = 0; k < pl.n; ++k) std::printf("%s%d", k ? ", " : "", pl.info[k]);
+      std::printf("], \"core\": [\"%a\", \"%a\", \"%a\", \"%a\"], \"tol\": \"%a\"", pl.x0, pl.x1, pl.z0, pl.z1, pl.tol);
+    }
     if (st == 0 && cs.place.hop_kind == 2) {
       rt::DGround g;
       std::memcpy(&g, cs.ground.data(), sizeof g);
