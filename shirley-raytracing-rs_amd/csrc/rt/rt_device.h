@@ -1068,7 +1068,9 @@ static __device__ unsigned long long g_phase_ctr[2 * kPhaseEvents];
 // histograms of the instrumented build: node visits per traversing lane, and per wave (its slowest lane)
 static __device__ unsigned long long g_visit_hist[64], g_wave_visit_hist[64];
 // wave-cycles inside the runs of the hop passes, by part (kHopClk*; trace.hip PH_PART)
-enum : int { kHopClkDownServe = 0, kHopClkDownNext = 1, kHopClkHopNext = 2, kHopClkHopServe = 3, kHopClks = 4 };
+// ... and inside leaf_tests4's RectBox loop and rect loop (kLeafClk*; PH_LOOP)
+enum : int { kHopClkDownServe = 0, kHopClkDownNext = 1, kHopClkHopNext = 2, kHopClkHopServe = 3, kLeafClkBox = 4,
+             kLeafClkRect = 5, kHopClks = 6 };
 static __device__ unsigned long long g_hop_clk[kHopClks];
 
 __device__ __forceinline__ void ph_count(int i) {
@@ -1083,8 +1085,17 @@ __device__ __forceinline__ void ph_count(int i) {
 #else  // (clock stamps only: the event atomics would dominate the phase clocks)
 #define PH_COUNT(i)
 #endif
+// a loop's wave-cycles: stamped around it by the lanes that reach it, added once per wave when one of them ran it
+#define PH_LOOP_BEGIN() const unsigned long long ph_loop0 = clock64()
+#define PH_LOOP_END(b, ran)                                                                                         \
+  do {                                                                                                              \
+    const unsigned long long ph_loop1 = clock64();                                                                  \
+    if (__ballot(ran) && (int)__lane_id() == __builtin_ctzll(__ballot(1))) atomicAdd(&g_hop_clk[b], ph_loop1 - ph_loop0); \
+  } while (0)
 #else
 #define PH_COUNT(i)
+#define PH_LOOP_BEGIN()
+#define PH_LOOP_END(b, ran)
 #endif
 // Per-lane node-visit / primitive-test statistics of the 4-wide traversal: counted in the instrumented
 // build only (they cost the production megakernel 0.5 %: ~15 VALU per iteration and two registers).
@@ -1276,17 +1287,23 @@ __device__ __forceinline__ unsigned top_bytes(unsigned w0, unsigned w1, unsigned
   return __builtin_amdgcn_perm(w1, w0, 0x0c0c0703u) | __builtin_amdgcn_perm(w3, w2, 0x07030c0cu);
 }
 
-template <int MODE, bool EXT, bool DEFER = false>
+template <int MODE, bool EXT, bool DEFER = false, bool GF = false>
 __device__ __forceinline__ void leaf_tests4(const DScene& S, const DPrim* lds_prims, v3 o, v3 d, v3 inv,
                                             RaySigns ns, const Recip& ra, bool ra_ok, double t_min, unsigned lm, int c0, int c1,
                                             int c2, int c3, const int32_t* chp, double& t_best, float& tmaxf, int& best,
                                             int& face_best, const Rng& rk, uint64_t seed, unsigned& ptests,
-                                            unsigned& xdefer) {
+                                            unsigned& xdefer, unsigned gkeep = ~0u) {
   // lm: spread mask of hit leaf children (bit 8 i + 7: child i).  A leaf's child word is
   // ~(prim | flags), so its generic / box flags (bits 29 / 28) are bits 5 / 4 of its top byte, inverted.
   const unsigned nf = ~top_bytes((unsigned)c0, (unsigned)c1, (unsigned)c2, (unsigned)c3);
   const unsigned gm = (nf << 2) & 0x80808080u, bm = (nf << 3) & 0x80808080u;
   unsigned sph = lm & ~gm, rect = lm & gm & ~bm, box = lm & bm;
+  // GF (the HOP = 4 megakernel instances): a lane whose ray plane_first answered holds G's hit already, and every
+  // rect and RectBox of a plane-stack scene belongs to G
+  if constexpr (GF) {
+    rect &= gkeep;
+    box &= gkeep;
+  }
   const bool div_ok = ra_ok;  // every |d_i| in range too (traverse4): faces divide through inv (face_div)
   bool hit = false;
   // nodes in LDS: child k's word read back from the node (one address op and one ds_read) instead of
@@ -1332,6 +1349,10 @@ __device__ __forceinline__ void leaf_tests4(const DScene& S, const DPrim* lds_pr
   // RectBox leaves before rect leaves: a box in front of a rect (the random scene's ground coat over its
   // lower surface, Cornell's blocks before its walls) then shrinks t_best first, so the rect's own box
   // test rejects without the rect test (+0.25 % headline)
+#ifdef RT_PHASE_TIMING
+  const bool ph_box = box != 0u, ph_rect = rect != 0u;
+#endif
+  PH_LOOP_BEGIN();
 #pragma unroll 1
   while (box) {
     PH_COUNT(7);
@@ -1372,6 +1393,9 @@ __device__ __forceinline__ void leaf_tests4(const DScene& S, const DPrim* lds_pr
                                          : box_t(pr.p, o, d, t_min, t_best, t, inv, div_ok);
     if (f >= 0 && tie_takes<EXT>(S, leaf, best, t, t_best, o, inv, ns, t_min)) { t_best = t; best = leaf; face_best = f; hit = true; }
   }
+  PH_LOOP_END(kLeafClkBox, ph_box);
+  {
+  PH_LOOP_BEGIN();
 #pragma unroll 1
   while (rect) {
     PH_COUNT(4);
@@ -1392,6 +1416,8 @@ __device__ __forceinline__ void leaf_tests4(const DScene& S, const DPrim* lds_pr
       default: h = rect_t<0, 2>(pr.p, o, d, t_min, t_best, t, inv, div_ok);
     }
     if (h && tie_takes<EXT>(S, leaf, best, t, t_best, o, inv, ns, t_min)) { t_best = t; best = leaf; face_best = -1; hit = true; }
+  }
+  PH_LOOP_END(kLeafClkRect, ph_rect);
   }
   if (hit) tmaxf = tmax_f32(t_best);
 }
@@ -1483,12 +1509,12 @@ __device__ __forceinline__ int node4_next(const DScene& S, int4 ch, float k0, fl
   top = stk[sp];
   return (int)(e & km);
 }
-template <int STRIDE, int MODE, bool EXT, bool DEFER = false>
+template <int STRIDE, int MODE, bool EXT, bool DEFER = false, bool GF = false>
 __device__ __forceinline__ int visit4(const DScene& S, const typename Node4Sel<EXT>::T* lds_nodes, const DPrim* lds_prims, v3 o, v3 d,
                                       v3 inv, RaySigns ns, const RayF& rf, const Recip& ra, bool ra_ok, double t_min, int node,
                                       double& t_best, float& tmaxf, int& best, int& face_best, int& sp,
                                       unsigned& top, unsigned* stk, const Rng& rk, uint64_t seed,
-                                      unsigned& visits, unsigned& ptests, unsigned& xdefer) {
+                                      unsigned& visits, unsigned& ptests, unsigned& xdefer, unsigned gkeep = ~0u) {
   int4 ch;
   float k0, k1, k2, k3;
   const int32_t* chp;
@@ -1496,8 +1522,8 @@ __device__ __forceinline__ int visit4(const DScene& S, const typename Node4Sel<E
                                         visits, chp);
   if (lm) PH_COUNT(1);
   if (lm)
-    leaf_tests4<MODE, EXT, DEFER>(S, lds_prims, o, d, inv, ns, ra, ra_ok, t_min, lm, ch.x, ch.y, ch.z, ch.w, chp, t_best, tmaxf,
-                                  best, face_best, rk, seed, ptests, xdefer);
+    leaf_tests4<MODE, EXT, DEFER, GF>(S, lds_prims, o, d, inv, ns, ra, ra_ok, t_min, lm, ch.x, ch.y, ch.z, ch.w, chp, t_best, tmaxf,
+                                      best, face_best, rk, seed, ptests, xdefer, gkeep);
   return node4_next<STRIDE, MODE != kSceneLds>(S, ch, k0, k1, k2, k3, tmaxf, sp, top, stk);
 }
 
@@ -1524,17 +1550,68 @@ __device__ __forceinline__ void ext_deferred(const DScene& S, unsigned xdefer, v
   }
 }
 
+// What the leaves of a plane stack's G return for a ray of the traversal itself (trace.hip HOP = 4 with
+// RT_GROUND_FIRST; rt_layout.h DPlanes; the proof: DESIGN.md §3.1), settled per lane before the first visit so that
+// the lane skips every rect and RectBox leaf (leaf_tests4 GF).  plane_hop_t's walk with its premises widened to
+// origins up to H above Y (y_max), on a core shrunk for that reach:
+//   kFirstNone  no primitive of G can be accepted: no plane lies ahead of the origin and beyond tol (an upward ray
+//               from above Y, a downward one from the lowest plane), or the ray starts above Y and crosses the
+//               highest plane outside the grown extent of G (over the edge);
+//   kFirstHit   the first plane ahead and beyond tol, whatever its hop answer: its primitive and face at
+//               t = RN((y_k - o.y) / d.y) through the prologue's 1 / d.y (face_div's form), when t > 2 t_min and the
+//               hit record's own point o + t d lies in the core;
+//   kFirstDecline  everything else — `ok` false (traverse4's ra_ok: every |d_i| in face_div's range, a near origin),
+//               an origin outside the core or [y_lo, y_max], |d.y| or the slope outside ground_hop_t's bounds: the
+//               lane runs the leaf tests as before.
+typedef __attribute__((address_space(4))) const DGround GGround;
+typedef __attribute__((address_space(4))) const DPlanes GPlanes;
+constexpr int kFirstDecline = 0, kFirstNone = 1, kFirstHit = 2;
+__device__ __forceinline__ int plane_first(GGround* g, GPlanes* pl, v3 o, v3 d, double inv_y, bool ok, double t_min,
+                                           double& t_out, int& prim, int& face) {
+  const double ay = fabs(d.y);
+  const double x0 = pl->fx0, x1 = pl->fx1, z0 = pl->fz0, z1 = pl->fz1;
+  if (!(ok && o.y >= g->y_lo && o.y <= pl->y_max && ay >= g->dy_min && ay <= 0x1p300 &&
+        d.x * d.x + d.z * d.z <= g->ratio2 * (d.y * d.y) && o.x >= x0 && o.x <= x1 && o.z >= z0 && o.z <= z1))
+    return kFirstDecline;
+  const bool up = d.y > 0.0;
+  const double tol = pl->tol, hi = o.y + tol, lo = o.y - tol;
+  double y = 0.0;
+  int info = -1;
+  const int n = pl->n;
+#pragma unroll 1
+  for (int k = 0; k < n; ++k) {
+    const double yk = pl->y[k];
+    const bool take = up ? (yk > hi && info < 0) : yk < lo;
+    y = take ? yk : y;
+    info = take ? pl->info[k] : info;
+  }
+  if (info < 0) return kFirstNone;
+  const double t = div_recip(y - o.y, Recip{d.y, inv_y});
+  if (!(t > 2.0 * t_min)) return kFirstDecline;
+  const double hx = o.x + t * d.x, hz = o.z + t * d.z;
+  if (!(hx >= x0 && hx <= x1 && hz >= z0 && hz <= z1)) {
+    // over the edge: from above Y the plane ahead is the highest one, and a crossing outside the grown extent of G
+    // leaves every primitive behind on that axis
+    const bool over = o.y > g->y_hi && (hx < pl->ox0 || hx > pl->ox1 || hz < pl->oz0 || hz > pl->oz1);
+    return over ? kFirstNone : kFirstDecline;
+  }
+  t_out = t;
+  prim = (int)((unsigned)info >> 5);
+  face = (info & 3) == 0 ? -1 : 3 + (info & 3);
+  return kFirstHit;
+}
+
 // Whole closest-hit query over the 4-wide tree (t_min > 0).  The conservative internal tests and the
 // exact leaf tests make the set of primitives that can win the reference's (see DNode4F); the closest
-// hit is the reference's up to exact ties in t.
-template <int STRIDE, int MODE, bool EXT>
+// hit is the reference's up to exact ties in t.  GF: G's answer first (plane_first), from the records gf_g / gf_pl.
+template <int STRIDE, int MODE, bool EXT, bool GF = false>
 __device__ __forceinline__ int traverse4(const DScene& S, const typename Node4Sel<EXT>::T* lds_nodes, const DPrim* lds_prims, v3 o, v3 d,
                                          double t_min, double& t_best, int& face_best, unsigned* stk,
                                          const Rng& rk, uint64_t seed, unsigned& visits, unsigned& ptests
 #ifdef RT_PHASE_TIMING
                                          , unsigned long long& trav_lane_steps_ref
 #endif
-                                         ) {
+                                         , GGround* gf_g = nullptr, GPlanes* gf_pl = nullptr) {
   PH_COUNT(23);
   bool inv_ok;
   const v3 inv = inv_dir(d, inv_ok);
@@ -1553,14 +1630,31 @@ __device__ __forceinline__ int traverse4(const DScene& S, const typename Node4Se
   unsigned top = ~0u;  // the stack's top entry (node4_next)
   int node = S.root4;
   unsigned xdefer = 0u;  // book-2: extended objects whose box passed, tested after the loop (leaf_tests4)
+  // GF: the loop starts from G's answer, and the lane's visits skip G's leaves.  The leaf tests are pure functions of
+  // (ray, t_min, t_best), so the closest hit is that of any other order; a sphere at exactly G's t meets tie_takes and
+  // mark_tie with best = G's leaf
+  unsigned gkeep = ~0u;  // (0: skip them; a mask in a VGPR — a bool would hold an SGPR pair across the loop)
+  if constexpr (GF) {
+    double tg;
+    int pg, fg;
+    const int k = plane_first(gf_g, gf_pl, o, d, inv.y, ra_ok, t_min, tg, pg, fg);
+    gkeep = k != kFirstDecline ? 0u : ~0u;
+    asm volatile("" : "+v"(gkeep));
+    if (k == kFirstHit && tg <= t_best) {
+      t_best = tg;
+      best = pg;
+      face_best = fg;
+      tmaxf = tmax_f32(tg);
+    }
+  }
   // a tree traversal visits every node at most once: more steps than nodes can only be a defect,
   // and ends the loop instead of hanging the wave
   for (int steps = 0; steps < S.n_nodes4 && node >= 0; ++steps) {
 #ifdef RT_PHASE_TIMING
     ++g_trav_lane_steps;
 #endif
-    node = visit4<STRIDE, MODE, EXT, EXT>(S, lds_nodes, lds_prims, o, d, inv, ns, rf, ra, ra_ok, t_min, node, t_best, tmaxf,
-                                          best, face_best, sp, top, stk, rk, seed, visits, ptests, xdefer);
+    node = visit4<STRIDE, MODE, EXT, EXT, GF>(S, lds_nodes, lds_prims, o, d, inv, ns, rf, ra, ra_ok, t_min, node, t_best, tmaxf,
+                                              best, face_best, sp, top, stk, rk, seed, visits, ptests, xdefer, gkeep);
   }
   if (EXT) ext_deferred(S, xdefer, o, d, inv, ns, t_min, t_best, best, face_best, rk, seed);
   if (best >= 0 && (best & kTieBit)) PH_COUNT(25);
@@ -1644,7 +1738,6 @@ __device__ __forceinline__ bool box_inward(int face, v3 d) {
   const double da = face < 2 ? d.z : (face < 4 ? d.x : d.y);
   return (face & 1) ? da > 0.0 : da < 0.0;
 }
-typedef __attribute__((address_space(4))) const DGround GGround;
 // DOWN (the down pass, trace.hip HOP = 3): the result is kHopServed for such a hit, and kHopFound when the closest hit
 // in G is no dielectric's, on an xz-rect or a RectBox y face whose plane lies at least `gap` below Y (y <= g->y_down),
 // under the same origin, |d.y| and slope conditions: the proof's "hits on planes below Y" never asks what the hit's
@@ -1733,7 +1826,6 @@ __device__ __forceinline__ bool ground_hop(const DScene& S, const DPrim* lds_pri
 // has an answer for that plane, t > 2 t_min, the hit record's own point o + t d lies inside the shrunk core and,
 // leaving through Y, its guard cell is free; DOWN as in ground_hop_t.  kHopRefused: the lane declines — the outputs
 // mean nothing and it traverses as before.
-typedef __attribute__((address_space(4))) const DPlanes GPlanes;
 template <bool DOWN>
 __device__ __forceinline__ int plane_hop_t(GGround* g, GPlanes* pl, v3 o, v3 d, double t_min, double& t_best, int& best,
                                            int& face_best, bool& guarded) {

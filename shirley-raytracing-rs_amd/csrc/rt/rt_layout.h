@@ -244,8 +244,17 @@ struct alignas(16) DPlanes {
   int32_t n, pad;
   double y[kGroundMaxPlanes];
   int32_t info[kGroundMaxPlanes];
+  // plane_first (rt_device.h; the traversal's own rays): the core shrunk by the margin of a segment
+  // that may start up to H above Y, and Y + H itself.  The hop passes keep the core above: their decisions do not
+  // depend on H.
+  double fx0, fx1, fz0, fz1;
+  double y_max;  // Y + H: an origin above it declines
+  // ... and the rectangle that holds every primitive's xz extent, grown by the margin mo: a ray from above Y that
+  // crosses the highest plane outside it has passed over the stack's edge and meets none of G
+  double ox0, ox1, oz0, oz1;
+  double pad2;
 };
-static_assert(sizeof(DPlanes) == 144, "DPlanes layout");
+static_assert(sizeof(DPlanes) == 224, "DPlanes layout");
 
 struct DCamera {
   int32_t width, height;   // image dims

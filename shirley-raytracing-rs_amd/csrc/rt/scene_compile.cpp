@@ -4,6 +4,7 @@
 #include "scene_compile.h"
 
 #include <algorithm>
+#include <cassert>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -594,6 +595,7 @@ bool sphere_never_hit(const double* p) { return p[3] <= 0.0 && p[1] - p[3] >= p[
 // (the proof's constants that plane_stack below builds on: gap, tol, reach and B, the largest |x|, |z| of G's extent)
 struct GroundConsts {
   double gap = 0.0, tol = 0.0, reach = 0.0, ext = 0.0;
+  double sph_top = 0.0;  // the highest plane of a sphere's leaf box (Y when the scene holds no sphere)
 };
 bool ground_stack(const std::vector<DPrim>& prims, int n_prims, std::vector<uint32_t>& out, GroundConsts* consts = nullptr) {
   out.clear();
@@ -661,6 +663,10 @@ bool ground_stack(const std::vector<DPrim>& prims, int n_prims, std::vector<uint
     consts->tol = tol;
     consts->reach = reach;
     consts->ext = std::max(std::max(std::fabs(ex0), std::fabs(ex1)), std::max(std::fabs(ez0), std::fabs(ez1)));
+    consts->sph_top = top;
+    for (int i = 0; i < n_prims; ++i)
+      if (prims[i].kind == kPrimSphere && !sphere_never_hit(prims[i].p))
+        consts->sph_top = std::max(consts->sph_top, prims[i].p[1] + prims[i].p[3]);
   }
 
   DGround g;
@@ -723,6 +729,9 @@ bool ground_stack(const std::vector<DPrim>& prims, int n_prims, std::vector<uint
 // mx = 2^-44 (B + reach + 1): 2^4 times the 2^-48 (B + L) of sphere_t_sure's eta, with the longest served segment's
 // horizontal run for L — far above the 3 * 2^-53 (B + reach) a hit point o + t d is off by, and above the
 // 2^-50 (B + reach) that keeps a side plane's quotient and slab product strictly behind the hit's.
+// The record's tail is plane_first's (the traversal's own rays, which may start up to H above Y): a second core, shrunk
+// for that longer reach, Y + H, and the grown extent of "over the edge".  Whether a stack is a plane stack, and the hop
+// passes' core, do not depend on it.
 bool plane_stack(const std::vector<DPrim>& prims, const std::vector<DMat>& mats, const std::vector<uint32_t>& ground,
                  const GroundConsts& k, std::vector<uint32_t>& out) {
   out.clear();
@@ -770,6 +779,28 @@ bool plane_stack(const std::vector<DPrim>& prims, const std::vector<DMat>& mats,
   d.tol = k.tol;
   d.n = (int32_t)pl.size();
   for (size_t i = 0; i < pl.size(); ++i) d.y[i] = pl[i].y, d.info[i] = pl[i].info;
+  // plane_first (rt_device.h): the traversal's rays start up to H above Y — H covers every point of the sphere boxes
+  // twice over, and at least 8 (random_scene's camera sits 2 above its ground) — so their longest segment runs
+  // H (R + 1) further than a hop's, and their core is shrunk by the margin of that reach.  An empty core (fx0 > fx1)
+  // makes every ray decline; the hop passes' core above is untouched.
+  const double height = std::min(0x1p20, std::max(8.0, 2.0 * (k.sph_top - g.y_top)));
+  const double reach_f = k.reach + height * (0x1p10 + 1.0);
+  const double mxf = 0x1p-44 * (k.ext + reach_f + 1.0);
+  d.fx0 = x0 + mxf, d.fx1 = x1 - mxf, d.fz0 = z0 + mxf, d.fz1 = z1 - mxf;
+  if (!(d.fx0 < d.fx1 && d.fz0 < d.fz1)) d.fx0 = d.fz0 = inf, d.fx1 = d.fz1 = -inf;
+  d.y_max = g.y_top + height;
+  // ... and "over the edge": the rectangle that holds every primitive's xz extent, grown by mo = 2^-23 (B + reach + 1).
+  // A crossing of the highest plane that far outside it puts every earlier side-plane crossing mo / R above that
+  // plane, 2^10 times the rounding of a hit point's y at the largest coordinates ground_stack admits (§3.1)
+  const double mo = 0x1p-23 * (k.ext + reach_f + 1.0);
+  double ux0 = inf, ux1 = -inf, uz0 = inf, uz1 = -inf;
+  for (int i = 0; i < g.n; ++i) {
+    const double* p = prims[g.prim[i]].p;
+    const bool bx = i < g.n_box;
+    ux0 = std::min(ux0, p[0]), ux1 = std::max(ux1, bx ? p[3] : p[1]);
+    uz0 = std::min(uz0, p[2]), uz1 = std::max(uz1, bx ? p[5] : p[3]);
+  }
+  d.ox0 = ux0 - mo, d.ox1 = ux1 + mo, d.oz0 = uz0 - mo, d.oz1 = uz1 + mo;
   out.assign(sizeof(DPlanes) / 4, 0u);
   std::memcpy(out.data(), &d, sizeof d);
   return true;
@@ -868,6 +899,16 @@ int plan_placement(const rt_scene_desc* d, int32_t placement, const SceneTuning&
   // ... both by the closed-form next plane (trace.hip, HOP = 4) where the stack is a plane stack (SHIRLEY_HOP=general:
   // never); a stack that misses a premise keeps the general passes
   P.hop_planes = P.hop_down && !tune.hop_general && plane_stack(cs.prims, cs.mats, cs.ground, consts, cs.planes);
+  if (P.hop_planes) {
+    // plane_first's premise (the HOP = 4 instances skip every rect and RectBox leaf of a lane it answered): each of
+    // them belongs to G — ground_stack admits no other, so this only fails if that rule changes
+    DGround g;
+    std::memcpy(&g, cs.ground.data(), sizeof g);
+    int n_flat = 0;
+    for (int i = 0; i < d->n_objects; ++i) n_flat += cs.prims[i].kind != kPrimSphere;
+    assert(n_flat == g.n);
+    if (n_flat != g.n) P.hop_planes = false;
+  }
   if (!P.hop_planes) cs.planes.clear();
 
   // wavefront extend block: its own (larger) stack area, the rest of LDS for nodes

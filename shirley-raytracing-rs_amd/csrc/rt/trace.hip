@@ -123,6 +123,11 @@ constexpr int kNarrowWaves = RT_NARROW_WAVES;
 #ifndef RT_HOP4_MIN_LANES_B
 #define RT_HOP4_MIN_LANES_B 8
 #endif
+// ... and, in the same two instances, the traversal itself settles the stack's primitives by closed form before its
+// first visit (rt_device.h plane_first, traverse4 GF).  0 builds the A/B partner (tools/variant.sh).
+#ifndef RT_GROUND_FIRST
+#define RT_GROUND_FIRST 1
+#endif
 #ifdef RT_HOP_SERVE_SHARED
 // A/B only: the serve body of the HOP = 3 instances as one call that the down pass and step 5' both
 // reach, instead of an inlined copy at each site.  Not built by default: the two inlined sites measured faster.
@@ -280,11 +285,21 @@ void trace_kernel(KParams P) {
     if constexpr (HOP >= 3) {
       static_assert(MODE == kSceneLds && !EXT, "the hop pass is built for the scene-in-LDS reference-scene instances");
       // (the pass's ballots need a wave-uniform point: this instance traverses here, not in the block below)
-      if (active)
-        prim = traverse4<THREADS, MODE, EXT>(S, lds_nodes, lds_prims, o, d, 0.001, t_best, face, stk, rng, seed, visits,
-                                             ptests RT_STAT_ARG(ph_lane_steps));
+      // (the stack's record: read before the traversal where the traversal itself asks it, else after, as before)
+      constexpr bool kFirst = HOP == 4 && RT_GROUND_FIRST;
+      GGround* g;
+      if constexpr (kFirst) g = (GGround*)kblock(P.kconst)->ground;
+      if (active) {
+        if constexpr (kFirst)
+          prim = traverse4<THREADS, MODE, EXT, true>(S, lds_nodes, lds_prims, o, d, 0.001, t_best, face, stk, rng, seed,
+                                                     visits, ptests RT_STAT_ARG(ph_lane_steps), g,
+                                                     (GPlanes*)kblock(P.kconst)->planes);
+        else
+          prim = traverse4<THREADS, MODE, EXT>(S, lds_nodes, lds_prims, o, d, 0.001, t_best, face, stk, rng, seed, visits,
+                                               ptests RT_STAT_ARG(ph_lane_steps));
+      }
       PH_STAMP(kPhTrav);
-      GGround* g = (GGround*)kblock(P.kconst)->ground;
+      if constexpr (!kFirst) g = (GGround*)kblock(P.kconst)->ground;
       bool pend = false;  // a dielectric hit of G in (prim, face, t_best), not shaded yet
       if (active && prim >= 0 && mats[lds_prims[prim].material].kind == RT_MAT_DIELECTRIC)
         for (int i = 0; i < g->n; ++i) pend = pend || g->prim[i] == prim;
@@ -1392,6 +1407,8 @@ void phase_counters_dump() {
             hop_serves ? (double)hc[kHopClkHopServe] / hop_serves : 0.0);
     fprintf(stderr, "[phase-run] wave-cycles in all: down serve %.4g, down next %.4g, hop next %.4g, hop serve %.4g\n", (double)hc[0],
             (double)hc[1], (double)hc[2], (double)hc[3]);
+    fprintf(stderr, "[phase-run] leaf_tests4 wave-cycles in all: RectBox loop %.4g, rect loop %.4g\n", (double)hc[kLeafClkBox],
+            (double)hc[kLeafClkRect]);
     unsigned long long zc[kHopClks] = {};
     (void)hipMemcpyToSymbol(HIP_SYMBOL(g_hop_clk), zc, sizeof zc);
   }

@@ -64,6 +64,19 @@ int main(int argc, char** argv) {
                 "\"hop_down\": %d, \"hop_planes\": %d, \"hop_instance\": %d", argv[a], st, cs.place.hop_pass ? 1 : 0,
                 cs.place.hop_kind, (int)cs.stats.hop_kind, cs.place.hop_down ? 1 : 0, cs.place.hop_planes ? 1 : 0,
                 rt::hop_instance(cs.place));
+    if (st == 0 && cs.exts.empty()) {
+      // the geometry kinds of the leaf children of the first 4-wide node a traversal visits (0 a sphere)
+      rt::DNode4F nd;
+      std::memcpy(&nd, cs.nodes4.data() + (size_t)cs.place.root4 * sizeof nd, sizeof nd);
+      std::printf(", \"root_leaf_kinds\": [");
+      bool first = true;
+      for (int k = 0; k < 4; ++k)
+        if (nd.child[k] < 0) {
+          std::printf("%s%d", first ? "" : ", ", (int)cs.prims[(~nd.child[k]) & rt::kLeafPrimMask].kind);
+          first = false;
+        }
+      std::printf("]");
+    }
     if (st == 0 && cs.place.hop_planes) {
       rt::DPlanes pl;
       std::memcpy(&pl, cs.planes.data(), sizeof pl);
@@ -72,6 +85,9 @@ int main(int argc, char** argv) {
       std::printf("], \"plane_info\": [");
       for (int k = 0; k < pl.n; ++k) std::printf("%s%d", k ? ", " : "", pl.info[k]);
       std::printf("], \"core\": [\"%a\", \"%a\", \"%a\", \"%a\"], \"tol\": \"%a\"", pl.x0, pl.x1, pl.z0, pl.z1, pl.tol);
+      // (plane_first's own core and origin-height bound)
+      std::printf(", \"core_first\": [\"%a\", \"%a\", \"%a\", \"%a\"], \"y_max\": \"%a\", \"outer\": [\"%a\", \"%a\", \"%a\", \"%a\"]", pl.fx0,
+                  pl.fx1, pl.fz0, pl.fz1, pl.y_max, pl.ox0, pl.ox1, pl.oz0, pl.oz1);
     }
     if (st == 0 && cs.place.hop_kind == 2) {
       rt::DGround g;
