@@ -1,10 +1,14 @@
 """Book-2 ("The Next Week") extensions: moving spheres, constant media, RotateY/Translate instances,
 the isotropic material and the book's final_scene (BASELINE config 5).
 
-None of these exist in the reference, so their parity is
-UNPINNED: these tests pin the oracle's restatement (oracle.c, "book-2 extensions") with analytic
-known answers, and pin the C++ host (bounding boxes, JSON, scene builder) against the oracle.
-The GPU parity tests (test_gpu_parity.py) then compare the HIP path with this oracle.
+None of these exist in the reference, so the oracle's form of them
+(oracle.c, "book-2 extensions") is a restatement of the book: these tests pin it with analytic known
+answers, and pin the C++ host (bounding boxes, JSON, scene builder) against the oracle;
+test_book2_scenes.py adds the oracle's tree against its plain list of objects and twin scenes whose frames
+must be equal.  The device is pinned against this oracle form by form — every base shape as a surface, an
+instance, a medium and an instanced medium, per-ray records bit for bit — by test_gpu_book2.py, and on the
+book's final_scene by test_gpu_parity.py.  What stays a restatement: the side streams of the ray time and the
+free flight, the medium's t_max test, front_face from the object frame.
 """
 import ctypes as C
 import json

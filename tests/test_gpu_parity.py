@@ -280,7 +280,9 @@ def test_hit_queries_match_oracle(gpu):
 
 def test_hit_queries_book2_match_oracle(gpu):
     """rt_scene_hit on the book-2 final scene (moving sphere at time 0, media keyed by the ray
-    index, rotated + translated cluster): same objects and records as the oracle."""
+    index, rotated + translated cluster): same objects and records as the oracle.  (The forms this scene does
+    not hold — instanced boxes and rects, box-bounded, instanced and moving media, rays from inside a medium —
+    and records with no exception: tests/test_gpu_book2.py test_hit_records_match_the_oracle.)"""
     scene = rt.scenes.final_scene(SEED, 8, 200).finalize(SEED)
     gpu.upload(scene)
     osc = O.OracleScene(scene)
