@@ -796,6 +796,88 @@ int rt_scene_light_pick(rt_ctx* ctx, int32_t cells, rt_light_grid* info);
  * light, n < 0, a NULL buffer with n > 0.  Blocks. */
 int rt_light_pick_at(rt_ctx* ctx, int32_t n, const double* points, const double* xi, int32_t* light, double* prob);
 
+/* ---- solid-angle sampling of sphere lights -----------------------------------------
+ * Added within ABI 11 like the light list: purely additive, RT_ABI_VERSION stays 11.
+ *
+ * A scene-level setting that rt_render_direct and rt_render_nee (host and _device forms) read, like
+ * rt_scene_light_pick and independent of it (all four combinations of pick and mode are valid).  In mode
+ * RT_LIGHT_SAMPLE_SOLID_ANGLE a sphere light's sample is a uniform direction of the cone the sphere subtends
+ * from the vertex, so every sample lands on the cap the vertex sees and the estimator has no cy / d2 factor.
+ * Rect lights are sampled as above in either mode.  rt_scene_upload resets the mode to RT_LIGHT_SAMPLE_AREA, so a
+ * caller that never sets it sees no change.
+ *
+ * IEEE binary64 throughout; only + - * /, a correctly rounded sqrt, comparisons and selects, in the order
+ * written (no fused multiply-add, no libm function).
+ * Light sample of a sphere light with centre c and radius r > 0 at a vertex (x, n), after the pick's draw D:
+ *   wc = c - x;  dc2 = (wc.x*wc.x + wc.y*wc.y) + wc.z*wc.z
+ *   inside     !(dc2 > r*r): the sample contributes 0, consumes no further draw and traces no ray; it still
+ *              counts as taken.
+ *   dc = sqrt(dc2);  a = wc / dc (per component)
+ *   s2 = (r*r) / dc2;  cm = sqrt(1.0 - s2);  om = s2 / (1.0 + cm)      (= 1 - cos(theta_max), no cancellation)
+ *   basis      sg = a.z < 0 ? -1.0 : 1.0;  A = -1.0 / (sg + a.z);  B = (a.x * a.y) * A
+ *              t1 = (1.0 + ((sg * a.x) * a.x) * A,  sg * B,  -(sg * a.x))
+ *              t2 = (B,  sg + (a.y * a.y) * A,  -a.y)                   (|sg + a.z| >= 1 always)
+ *   disk       (px, py) = random_in_unit_disk on draws D+1, ... (two per attempt, each -1 + 2 * draw, accepted
+ *              when px*px + py*py <= 1: the camera lens's function)
+ *   q = px*px + py*py;  e = q * om;  ct = 1.0 - e;  k = sqrt(om * (1.0 + ct))
+ *              (q is uniform on [0, 1] and independent of the disk point's angle, so no sin / cos is needed:
+ *              ct = cos(theta) is uniform on [1 - om, 1], and (px, py) * k = sin(theta) * (cos(phi), sin(phi)))
+ *   omega = (t1 * (px * k) + t2 * (py * k)) + a * ct                    (per component, in this order)
+ *   st2 = e * (1.0 + ct);  disc = r*r - dc2 * st2;  disc = disc > 0 ? disc : 0
+ *   ds = dc * ct - sqrt(disc);  w = omega * ds
+ *   u = ((x + w) - c) / r (per component)
+ *   then as in rt_render_direct: d2 = len2(w); dist = sqrt(d2); cx = dot(n, w) / dist; cy = -dot(u, w) / dist;
+ *              the cut !(cx > 0 && cy > 0); the shadow ray (x, w) on [0.001, 1 - 2^-20]; Le (FairyLight:
+ *              colour * cy).
+ *   value      RT_NEE_MIS clear and rt_render_direct:
+ *                g = cx * ((2.0 * om) * (double)L)           grid pick: g = cx * ((2.0 * om) / p)
+ *              RT_NEE_MIS set:
+ *                gs = cx / pi;  pl = 1.0 / (((2.0 * pi) * om) * (double)L)      grid pick: pl = p / ((2.0 * pi) * om)
+ *                g = gs / (pl + gs)
+ *              value_c = (a_c * Le_c) * g
+ * Emission weight (rt_render_nee): when the hit is a listed sphere, front_face holds and the previous vertex took
+ * a sample, with o the origin of the segment's ray (the previous vertex): wc = c - o, dc2, s2, cm, om as above;
+ *   !(dc2 > r*r) or !(cx_prev > 0):  ws = 1;
+ *   else RT_NEE_MIS set:    gs = cx_prev / pi;  pl as above, with p_j(cell_prev) under the grid pick;
+ *                           ws = gs / (pl + gs);
+ *   else RT_NEE_MIS clear:  ws = 0.
+ * Rect hits and everything else keep rt_render_nee's text.
+ * Why it is unbiased: the cone's solid angle is 2 pi om, so the light sample's solid-angle density is
+ * 1 / (2 pi om) per pick (times 1 / L or p for the pick) over exactly the directions that meet the sphere; the
+ * plain estimator is f cos / density = (a / pi) Le cx (2 pi om) / pick.  The Lambertian scatter's density is cx / pi per solid angle, and the weights are the balance heuristic
+ * in that measure at the previous vertex — the measure changes, the two densities' ratio does not.  From inside a
+ * sphere both modes give the light sample nothing (area: cy <= 0 everywhere), and the scatter keeps the emission
+ * whole. */
+enum { RT_LIGHT_SAMPLE_AREA = 0, RT_LIGHT_SAMPLE_SOLID_ANGLE = 1 };
+/* Sets how rt_render_direct / rt_render_nee sample the uploaded scene's sphere lights until the next
+ * rt_scene_upload or rt_scene_light_sampling.  RT_E_INVALID: no uploaded scene, an unknown mode (the setting is
+ * then left as it was).  Blocks until work queued on the context's stream has finished. */
+int rt_scene_light_sampling(rt_ctx* ctx, int32_t mode);
+/* Test entry points like rt_light_pick_at: vertex i = (points[i], normals[i]) runs the whole light sample except
+ * the shadow ray, on the path key (seed, pixel = i, sample = 0) from draw 0, with a = 1 and no emitter scaling.
+ *   light     the light picked;  draws: the path's draw counter after the sample.
+ *   flags     1: cut, !(cx > 0 && cy > 0);  2: inside (solid-angle mode).  g_plain = g_mis = 0 with either;
+ *             inside also leaves w, cx and cy 0.
+ *   g_plain   g with RT_NEE_MIS clear;  g_mis: g with it set.
+ * rt_light_sample_at runs on the device under the scene's current pick and mode.  rt_light_sample_host is plain
+ * C++ without a device, compiled without contraction, and takes the pick (cells: 0 uniform, 1 ... 64 the grid)
+ * and the mode as arguments.  RT_E_INVALID: no uploaded scene / a NULL or invalid scene, no listed light, n < 0, a
+ * NULL buffer with n > 0, cells or mode out of range, a table of more than 2^22 entries.  n == 0 is RT_OK.
+ * rt_light_sample_at blocks. */
+typedef struct rt_light_sample {
+  int32_t light;
+  int32_t flags;
+  uint32_t draws;
+  int32_t pad;
+  double w[3];
+  double cx, cy;
+  double g_plain, g_mis;
+} rt_light_sample;
+int rt_light_sample_at(rt_ctx* ctx, int32_t n, const double* points, const double* normals, uint64_t seed,
+                       rt_light_sample* out);
+int rt_light_sample_host(const rt_scene_desc* scene, int32_t cells, int32_t mode, int32_t n, const double* points,
+                         const double* normals, uint64_t seed, rt_light_sample* out);
+
 #ifdef __cplusplus
 }
 #endif

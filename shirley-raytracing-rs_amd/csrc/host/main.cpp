@@ -30,6 +30,7 @@
 // the same restrictions as --direct, and not together with it.
 // --light-grid N (with --nee or --direct): the spatially weighted light pick (rt_scene_light_pick) with N cells,
 // 1 ... 64, along the light grid's longest axis; 0, the default, is the uniform pick.
+// --light-cone (with --nee or --direct): sphere lights are sampled by solid angle (rt_scene_light_sampling).
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -67,6 +68,7 @@ struct Args {
   int nee_mis = 1;
   int light_grid = 0;  // --light-grid N: the light pick of --nee / --direct (0: uniform)
   bool light_grid_given = false;
+  bool light_cone = false;  // --light-cone: solid-angle sampling of sphere lights in --nee / --direct
   double fov = 20.0, focal = 1.0, aperture = 0.001;
   bool night = false, single_threaded = false;
   unsigned long long seed = 0x5EED;
@@ -87,7 +89,8 @@ struct Args {
                "         --ao RADIUS|inf --ao-chain K\n"
                "         --direct --direct-chain K\n"
                "         --nee --nee-mis 0|1\n"
-               "         --light-grid N (with --nee or --direct; 0 ... 64 cells, 0 = uniform pick)\n");
+               "         --light-grid N (with --nee or --direct; 0 ... 64 cells, 0 = uniform pick)\n"
+               "         --light-cone (with --nee or --direct: sphere lights sampled by solid angle)\n");
   std::exit(2);
 }
 
@@ -372,6 +375,11 @@ int render_scene(const Args& a, const rt_scene_desc* desc, const rt_camera& cam)
     rt_destroy(ctx);
     return 1;
   }
+  if ((a.direct || a.nee) && a.light_cone && (st = rt_scene_light_sampling(ctx, RT_LIGHT_SAMPLE_SOLID_ANGLE))) {
+    std::fprintf(stderr, "error: --light-cone: %s\n", rt_last_error(ctx));
+    rt_destroy(ctx);
+    return 1;
+  }
   if (a.direct) {
     // the direct-lighting pass in place of the colour render: emission + direct through the tonemap
     std::vector<double> direct(n);
@@ -611,6 +619,7 @@ int main(int argc, char** argv) {
       a.light_grid = std::atoi(next().c_str());
       a.light_grid_given = true;
     }
+    else if (s == "--light-cone") a.light_cone = true;
     else if (s == "--partition") {
       const std::string v = next();
       if (v == "tiles") a.partition = RT_PARTITION_TILES;
@@ -665,6 +674,7 @@ int main(int argc, char** argv) {
   if (a.direct && !a.dump_accum.empty()) usage("--direct frames are not checkpointed (--dump-accum)");
   if (a.direct_chain < 0) usage("--direct-chain K >= 0");
 
+  if (a.light_cone && !(a.nee || a.direct)) usage("--light-cone sets the light sampling of --nee or --direct");
   if (a.light_grid_given && !(a.nee || a.direct)) usage("--light-grid sets the light pick of --nee or --direct");
   if (a.light_grid < 0 || a.light_grid > 64) usage("--light-grid N in 0 ... 64");
 

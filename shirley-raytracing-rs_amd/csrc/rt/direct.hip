@@ -10,7 +10,9 @@
 // size and launch are the frame's (pass_frame.h); the kernel spells the frame's device pieces out, because with
 // any of them it runs 0.5 % slower on the night frame (profiles/passframe/direct_pieces.json).
 // Reference scenes only (no book-2 records): EXT = false instances.
-// light_pick_kernel (rt_light_pick_at) runs the grid's pick alone, one point per lane.
+// A kSampleCone instance (light_cone.h) samples sphere lights by solid angle.
+// light_pick_kernel (rt_light_pick_at) runs the grid's pick alone, one point per lane; light_sample_kernel
+// (rt_light_sample_at) the whole light sample but its shadow ray.
 #include <hip/hip_runtime.h>
 
 #include "direct.h"
@@ -19,7 +21,7 @@
 
 namespace rt {
 
-template <int THREADS, int MODE, int PICK>
+template <int THREADS, int MODE, int PICK, int SAMPLE>
 __global__ __launch_bounds__(THREADS) void direct_kernel(DScene S, DCamera C, uint64_t seed, int s_begin, int s_end,
                                                          int chain, int tiles_x, int n_tiles,
                                                          const DLight* __restrict__ lights, int n_lights,
@@ -117,8 +119,8 @@ __global__ __launch_bounds__(THREADS) void direct_kernel(DScene S, DCamera C, ui
             a = unit(a);
           }
           if (n_lights > 0)
-            dl = direct_light<THREADS, MODE, PICK>(S, lds_nodes, lds_prims, lights, n_lights, rng, seed, h.point,
-                                                   h.normal, a, stk, visits, ptests, grid);
+            dl = direct_light<THREADS, MODE, PICK, SAMPLE>(S, lds_nodes, lds_prims, lights, n_lights, rng, seed,
+                                                           h.point, h.normal, a, stk, visits, ptests, grid);
         }
       }
       se = se + em;
@@ -140,10 +142,10 @@ __global__ __launch_bounds__(THREADS) void direct_kernel(DScene S, DCamera C, ui
 }
 
 // rt_render_direct
-// rt_render_direct; `grid` (null: the uniform pick) is read only where n_lights > 0
+// rt_render_direct; `grid` (null: the uniform pick) is read only where n_lights > 0; `cone`: the kSampleCone instances
 hipError_t launch_direct(const DScene& S, bool wide, const DCamera& C, uint64_t seed, int s_begin, int s_end, int chain,
-                         const DLight* lights, int n_lights, const DLightGrid* grid, double* emission, double* direct,
-                         hipStream_t stream) {
+                         const DLight* lights, int n_lights, const DLightGrid* grid, bool cone, double* emission,
+                         double* direct, hipStream_t stream) {
   if (S.exts) return hipErrorInvalidValue;  // (the caller refuses book-2 scenes)
   if (n_lights > 0 && !lights) return hipErrorInvalidValue;
   if (grid && n_lights > 0 && !grid->cdf) return hipErrorInvalidValue;
@@ -154,8 +156,11 @@ hipError_t launch_direct(const DScene& S, bool wide, const DCamera& C, uint64_t 
       return launch_block(kernel, G.blocks(T), T, block_lds_bytes<M>(S, node4_bytes(false), T), stream, S, C, seed,
                           s_begin, s_end, chain, G.tiles_x, G.n_tiles, lights, n_lights, emission, direct, g);
     };
-    return grid && n_lights > 0 ? go(direct_kernel<T, M, kPickGrid>, *grid)
-                                : go(direct_kernel<T, M, kPickUniform>, NoLightGrid{});
+    if (cone)
+      return grid && n_lights > 0 ? go(direct_kernel<T, M, kPickGrid, kSampleCone>, *grid)
+                                  : go(direct_kernel<T, M, kPickUniform, kSampleCone>, NoLightGrid{});
+    return grid && n_lights > 0 ? go(direct_kernel<T, M, kPickGrid, kSampleArea>, *grid)
+                                : go(direct_kernel<T, M, kPickUniform, kSampleArea>, NoLightGrid{});
   });
 }
 
@@ -180,6 +185,54 @@ hipError_t launch_light_pick(const DLightGrid& grid, int n_lights, int n, const 
   if (n_lights < 1 || !grid.cdf || !points || !xi || !light || !prob) return hipErrorInvalidValue;
   return launch_block(light_pick_kernel, (n + kHitThreads - 1) / kHitThreads, kHitThreads, 0, stream, grid, n_lights, n,
                       points, xi, light, prob);
+}
+
+// rt_light_sample_at: one vertex per lane on the path key (seed, pixel = i, sample 0) from draw 0 — the whole
+// light sample but its shadow ray (light_sample_point, then both forms of light_sample_g).
+template <int PICK, int SAMPLE>
+__global__ __launch_bounds__(kHitThreads) void light_sample_kernel(const DLight* __restrict__ lights, int n_lights,
+                                                                   uint64_t seed, int n,
+                                                                   const double* __restrict__ points,
+                                                                   const double* __restrict__ normals,
+                                                                   rt_light_sample* __restrict__ out,
+                                                                   const typename PickGrid<PICK>::type grid) {
+  const int i = blockIdx.x * kHitThreads + (int)threadIdx.x;
+  if (i >= n) return;
+  const double* p = points + (size_t)i * 3;
+  const double* q = normals + (size_t)i * 3;
+  Rng rng{(uint32_t)i, 0u, 0u, 0u, 0u};
+  int cell = 0;
+  const LightSample s =
+      light_sample_point<PICK, SAMPLE>(lights, n_lights, rng, seed, V(p[0], p[1], p[2]), V(q[0], q[1], q[2]), grid, cell);
+  rt_light_sample r;
+  r.light = s.li;
+  r.flags = s.flags;
+  r.draws = rng.draw;
+  r.pad = 0;
+  r.w[0] = s.w.x;
+  r.w[1] = s.w.y;
+  r.w[2] = s.w.z;
+  r.cx = s.cx;
+  r.cy = s.cy;
+  r.g_plain = s.flags ? 0.0 : light_sample_g<false, PICK, SAMPLE>(lights[s.li], s, (double)n_lights);
+  r.g_mis = s.flags ? 0.0 : light_sample_g<true, PICK, SAMPLE>(lights[s.li], s, (double)n_lights);
+  out[i] = r;
+}
+
+hipError_t launch_light_sample(const DLight* lights, int n_lights, const DLightGrid* grid, bool cone, uint64_t seed,
+                               int n, const double* points, const double* normals, rt_light_sample* out,
+                               hipStream_t stream) {
+  if (n <= 0) return hipSuccess;
+  if (n_lights < 1 || !lights || !points || !normals || !out || (grid && !grid->cdf)) return hipErrorInvalidValue;
+  auto go = [&](auto kernel, auto g) {
+    return launch_block(kernel, (n + kHitThreads - 1) / kHitThreads, kHitThreads, 0, stream, lights, n_lights, seed, n,
+                        points, normals, out, g);
+  };
+  if (cone)
+    return grid ? go(light_sample_kernel<kPickGrid, kSampleCone>, *grid)
+                : go(light_sample_kernel<kPickUniform, kSampleCone>, NoLightGrid{});
+  return grid ? go(light_sample_kernel<kPickGrid, kSampleArea>, *grid)
+              : go(light_sample_kernel<kPickUniform, kSampleArea>, NoLightGrid{});
 }
 
 }  // namespace rt

@@ -14,6 +14,8 @@
 // take more.  The light table and the primitive -> light table are kernel arguments of their own, and so is the
 // light grid of a kPickGrid instance (light_pick.h, DESIGN.md §18: the last argument, an empty record in the
 // uniform instances), whose path state holds one more integer: the cell of the vertex that took the light sample.
+// A kSampleCone instance (light_cone.h, DESIGN.md §19: rt_scene_light_sampling) samples sphere lights by solid
+// angle and weights a listed sphere hit from the cone that sphere subtends at the segment's origin.
 #include <hip/hip_runtime.h>
 
 #include "direct.h"
@@ -22,7 +24,7 @@
 
 namespace rt {
 
-template <int THREADS, int MODE, bool MIS, int PICK>
+template <int THREADS, int MODE, bool MIS, int PICK, int SAMPLE>
 __global__ __launch_bounds__(THREADS) void nee_kernel(DScene S, DCamera C, uint64_t seed, int s_begin, int s_end,
                                                       int max_depth, int tiles_x, int n_tiles,
                                                       const DLight* __restrict__ lights, int n_lights,
@@ -104,6 +106,7 @@ __global__ __launch_bounds__(THREADS) void nee_kernel(DScene S, DCamera C, uint6
         done = true;
       } else {
         const v3 din = d;  // the segment's direction (shade_factor replaces the ray)
+        const v3 oin = o;  // ... and its origin, the previous vertex (read by a kSampleCone instance only)
         bool has_emit = false;
         v3 mul = V(1.0, 1.0, 1.0), emit = V(0.0, 0.0, 0.0);
         const bool alive = shade_factor(S, S.texs, S.mats[mat], leaf, pn, rs, un, rng, o, d, h, prim, face, mul, emit,
@@ -112,7 +115,27 @@ __global__ __launch_bounds__(THREADS) void nee_kernel(DScene S, DCamera C, uint6
           double ws = 1.0;
           const int lj = prev ? prim_light[prim] : -1;
           if (lj >= 0 && (lights[lj].geometry != RT_GEOM_SPHERE || h.front_face)) {
-            if (MIS) {
+            if (SAMPLE == kSampleCone && lights[lj].geometry == RT_GEOM_SPHERE) {
+              // both densities per solid angle at the previous vertex: the scatter's cx_prev / pi, the light
+              // sample's 1 / (2 pi om) per pick; from inside the sphere the light sample gave nothing
+              const DLight& Lj = lights[lj];
+              c3 wc;
+              double dc2, om;
+              if (cone_open(c3{Lj.p[0], Lj.p[1], Lj.p[2]}, Lj.p[3], c3{oin.x, oin.y, oin.z}, wc, dc2, om) &&
+                  cx_prev > 0.0) {
+                if (MIS) {
+                  const double gs = cx_prev / kDirectPi;
+                  double pl;
+                  if constexpr (PICK == kPickGrid)
+                    pl = light_prob(grid, cell_prev, n_lights, lj) / ((2.0 * kDirectPi) * om);
+                  else
+                    pl = 1.0 / (((2.0 * kDirectPi) * om) * (double)n_lights);
+                  ws = gs / (pl + gs);
+                } else {
+                  ws = 0.0;
+                }
+              }
+            } else if (MIS) {
               const double ld2 = (din.x * din.x + din.y * din.y) + din.z * din.z;
               const double ld = sqrt_rn(ld2);
               const double cy = -dot(h.normal, din) / ld;
@@ -138,9 +161,9 @@ __global__ __launch_bounds__(THREADS) void nee_kernel(DScene S, DCamera C, uint6
           prev = false;
           if ((mk == RT_MAT_LAMBERTIAN || mk == RT_MAT_FAIRY_LIGHT) && n_lights > 0 && k < max_depth) {
             // on the path's draws after the scatter's own; stands for segment k + 1's emission
-            const v3 dl = direct_light<THREADS, MODE, MIS, PICK>(S, L.nodes, L.prims, lights, n_lights, rng, seed,
-                                                                 h.point, h.normal, mul, L.stk, visits, ptests, prev,
-                                                                 grid, cell_prev);
+            const v3 dl = direct_light<THREADS, MODE, MIS, PICK, SAMPLE>(S, L.nodes, L.prims, lights, n_lights, rng,
+                                                                         seed, h.point, h.normal, mul, L.stk, visits,
+                                                                         ptests, prev, grid, cell_prev);
             rad = rad + hmul(att, dl);
             cx_prev = dot(h.normal, d) / sqrt_rn(len2(d));
           }
@@ -163,9 +186,9 @@ __global__ __launch_bounds__(THREADS) void nee_kernel(DScene S, DCamera C, uint6
   accum[p * 3 + 2] = sum.z;
 }
 
-// rt_render_nee; `grid` (null: the uniform pick) is read only where n_lights > 0
+// rt_render_nee; `grid` (null: the uniform pick) is read only where n_lights > 0; `cone`: the kSampleCone instances
 hipError_t launch_nee(const DScene& S, bool wide, bool mis, const DCamera& C, uint64_t seed, int s_begin, int s_end,
-                      int max_depth, const DLight* lights, int n_lights, const DLightGrid* grid,
+                      int max_depth, const DLight* lights, int n_lights, const DLightGrid* grid, bool cone,
                       const int32_t* prim_light, double* accum, hipStream_t stream) {
   if (S.exts) return hipErrorInvalidValue;  // (the caller refuses book-2 scenes)
   if (!accum || !prim_light || (n_lights > 0 && !lights)) return hipErrorInvalidValue;
@@ -177,10 +200,15 @@ hipError_t launch_nee(const DScene& S, bool wide, bool mis, const DCamera& C, ui
       return launch_block(kernel, G.blocks(T), T, block_lds_bytes<M>(S, node4_bytes(false), T), stream, S, C, seed,
                           s_begin, s_end, max_depth, G.tiles_x, G.n_tiles, lights, n_lights, prim_light, accum, g);
     };
-    if (grid && n_lights > 0)
-      return mis ? go(nee_kernel<T, M, true, kPickGrid>, *grid) : go(nee_kernel<T, M, false, kPickGrid>, *grid);
-    return mis ? go(nee_kernel<T, M, true, kPickUniform>, NoLightGrid{})
-               : go(nee_kernel<T, M, false, kPickUniform>, NoLightGrid{});
+    auto pick = [&](auto sample) {
+      constexpr int SM = decltype(sample)::value;
+      if (grid && n_lights > 0)
+        return mis ? go(nee_kernel<T, M, true, kPickGrid, SM>, *grid)
+                   : go(nee_kernel<T, M, false, kPickGrid, SM>, *grid);
+      return mis ? go(nee_kernel<T, M, true, kPickUniform, SM>, NoLightGrid{})
+                 : go(nee_kernel<T, M, false, kPickUniform, SM>, NoLightGrid{});
+    };
+    return cone ? pick(std::integral_constant<int, kSampleCone>{}) : pick(std::integral_constant<int, kSampleArea>{});
   });
 }
 

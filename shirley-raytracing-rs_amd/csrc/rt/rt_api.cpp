@@ -619,6 +619,7 @@ int rt_scene_upload(rt_ctx* c, const rt_scene_desc* d, int32_t builder) {
   c->light_list = std::move(cs.lights.lights);
   c->light_dev = std::move(cs.lights.dev);
   c->light_cells = 0;  // every upload starts with the uniform pick (rt_scene_light_pick)
+  c->light_sampling = RT_LIGHT_SAMPLE_AREA;  // ... and with area sampling (rt_scene_light_sampling)
   c->n_unlisted_lights = cs.lights.n_unlisted;
   c->stats = cs.stats;
   c->digest = cs.digest;

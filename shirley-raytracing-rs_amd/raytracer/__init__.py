@@ -10,5 +10,6 @@ from .scene import (SceneBuilder, Scene, TextureLoader, Metal, Dielectric, Lambe
                     Isotropic, MovingSphere, ConstantMedium, Transform)
 from .camera import CameraBuilder, CameraPosition, default_camera, cornell_camera, scene_camera  # noqa: F401
 from .render import (Device, RenderSettings, AdaptiveSettings, Comm, render_scene, render_multi, comm_unique_id, scene_digest, to_image,  # noqa: F401
-                     to_image_counts, write_png, tile_layout, DenoiseSettings, denoise, moments_variance, light_grid_host)
+                     to_image_counts, write_png, tile_layout, DenoiseSettings, denoise, moments_variance, light_grid_host,
+                     light_sample_host)
 from . import scenes  # noqa: F401

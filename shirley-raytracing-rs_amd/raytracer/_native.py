@@ -27,6 +27,7 @@ RT_ENGINE_AUTO, RT_ENGINE_MEGAKERNEL, RT_ENGINE_WAVEFRONT, RT_ENGINE_SPLIT, RT_E
 RT_TRAVERSAL_BINARY, RT_TRAVERSAL_RENDER = 0, 1
 RT_PARTITION_AUTO, RT_PARTITION_TILES, RT_PARTITION_SAMPLES = 0, 1, 2
 RT_NEE_MIS = 1  # rt_render_nee flags
+RT_LIGHT_SAMPLE_AREA, RT_LIGHT_SAMPLE_SOLID_ANGLE = 0, 1  # rt_scene_light_sampling modes
 
 _d3 = C.c_double * 3
 _d6 = C.c_double * 6
@@ -133,6 +134,11 @@ class rt_light(C.Structure):  # the scene's light list (added within ABI 11)
 
 class rt_light_grid(C.Structure):  # the light grid of rt_scene_light_pick (added within ABI 11)
     _fields_ = [("n", C.c_int32 * 3), ("n_lights", C.c_int32), ("lo", _d3), ("hi", _d3)]
+
+
+class rt_light_sample(C.Structure):  # a light sample before its shadow ray (added within ABI 11)
+    _fields_ = [("light", C.c_int32), ("flags", C.c_int32), ("draws", C.c_uint32), ("pad", C.c_int32), ("w", _d3),
+                ("cx", C.c_double), ("cy", C.c_double), ("g_plain", C.c_double), ("g_mis", C.c_double)]
 
 
 class rt_bvh_node(C.Structure):
@@ -242,6 +248,12 @@ RT_SIGNATURES = {
     "rt_light_grid_host": (C.c_int, [C.POINTER(rt_scene_desc), C.c_int32, C.POINTER(rt_light_grid), C.c_void_p]),
     "rt_scene_light_pick": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(rt_light_grid)]),
     "rt_light_pick_at": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # added within ABI 11: solid-angle sampling of sphere lights
+    "rt_scene_light_sampling": (C.c_int, [C.c_void_p, C.c_int32]),
+    "rt_light_sample_at": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_uint64,
+                                     C.POINTER(rt_light_sample)]),
+    "rt_light_sample_host": (C.c_int, [C.POINTER(rt_scene_desc), C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                       C.c_void_p, C.c_uint64, C.POINTER(rt_light_sample)]),
 }
 
 # every symbol declared in include/shirley_host.h

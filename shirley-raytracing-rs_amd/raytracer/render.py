@@ -399,6 +399,20 @@ class Device:
                                                      prob.ctypes.data))
         return light[:len(p)], prob[:len(p)]
 
+    def light_sampling(self, mode: int) -> None:
+        """rt_scene_light_sampling: how render_direct / render_nee sample a sphere light until the next upload():
+        N.RT_LIGHT_SAMPLE_AREA (a point of its area) or N.RT_LIGHT_SAMPLE_SOLID_ANGLE (a direction of the cone it
+        subtends from the vertex; include/shirley_rt.h).  Rect lights are sampled by area either way."""
+        _check(self._h, N.rt_lib().rt_scene_light_sampling(self._h, int(mode)))
+
+    def light_sample_at(self, points: np.ndarray, normals: np.ndarray, seed: int):
+        """rt_light_sample_at: the device's light sample without its shadow ray -> rt_light_sample array, vertex i
+        on the path key (seed, pixel = i, sample 0), under the pick and mode last set."""
+        p, n = _vertices(points, normals)
+        out = (N.rt_light_sample * max(1, len(p)))()
+        _check(self._h, N.rt_lib().rt_light_sample_at(self._h, len(p), p.ctypes.data, n.ctypes.data, int(seed), out))
+        return out[:len(p)]
+
     def probe(self, rays: np.ndarray, seed: int, sample: int = 0, draw: int = 0):
         """One iteration of ray_color's loop (render.rs:30-46) per ray through the megakernel's device code
         (rt_probe_segment): ray i on the path key (seed, pixel = i, sample, draw) -> rt_probe array
@@ -490,6 +504,26 @@ def light_grid_host(scene: Scene, cells: int):
         if code:
             raise N.RtError(code, "rt_light_grid_host failed")
     return info, cdf
+
+
+def _vertices(points, normals):
+    p = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+    n = np.ascontiguousarray(normals, dtype=np.float64).reshape(-1, 3)
+    if len(p) != len(n):
+        raise ValueError("one normal per point")
+    return p, n
+
+
+def light_sample_host(scene: Scene, cells: int, mode: int, points, normals, seed: int):
+    """rt_light_sample_host -> rt_light_sample array: what Device.light_sample_at computes after light_pick(cells)
+    and light_sampling(mode), in plain C++ (no device needed)."""
+    p, n = _vertices(points, normals)
+    out = (N.rt_light_sample * max(1, len(p)))()
+    code = N.rt_lib().rt_light_sample_host(scene.desc_ptr, int(cells), int(mode), len(p), p.ctypes.data,
+                                           n.ctypes.data, int(seed), out)
+    if code:
+        raise N.RtError(code, "rt_light_sample_host: invalid scene, cells or mode, or no listed light")
+    return out[:len(p)]
 
 
 def tile_layout(camera: N.rt_camera, world: int):
