@@ -803,8 +803,9 @@ int rt_light_pick_at(rt_ctx* ctx, int32_t n, const double* points, const double*
  * rt_scene_light_pick and independent of it (all four combinations of pick and mode are valid).  In mode
  * RT_LIGHT_SAMPLE_SOLID_ANGLE a sphere light's sample is a uniform direction of the cone the sphere subtends
  * from the vertex, so every sample lands on the cap the vertex sees and the estimator has no cy / d2 factor.
- * Rect lights are sampled as above in either mode.  rt_scene_upload resets the mode to RT_LIGHT_SAMPLE_AREA, so a
- * caller that never sets it sees no change.
+ * Rect lights are sampled as above in both of these modes; RT_LIGHT_SAMPLE_SOLID_ANGLE_ALL (further below) samples
+ * them by solid angle too.  rt_scene_upload resets the mode to RT_LIGHT_SAMPLE_AREA, so a caller that never sets it
+ * sees no change.
  *
  * IEEE binary64 throughout; only + - * /, a correctly rounded sqrt, comparisons and selects, in the order
  * written (no fused multiply-add, no libm function).
@@ -849,15 +850,85 @@ int rt_light_pick_at(rt_ctx* ctx, int32_t n, const double* points, const double*
  * sphere both modes give the light sample nothing (area: cy <= 0 everywhere), and the scatter keeps the emission
  * whole. */
 enum { RT_LIGHT_SAMPLE_AREA = 0, RT_LIGHT_SAMPLE_SOLID_ANGLE = 1 };
-/* Sets how rt_render_direct / rt_render_nee sample the uploaded scene's sphere lights until the next
- * rt_scene_upload or rt_scene_light_sampling.  RT_E_INVALID: no uploaded scene, an unknown mode (the setting is
- * then left as it was).  Blocks until work queued on the context's stream has finished. */
+
+/* ---- solid-angle sampling of rect lights -------------------------------------------
+ * Added within ABI 11 like the light list: purely additive, RT_ABI_VERSION stays 11.
+ *
+ * A third mode of the same setting.  RT_LIGHT_SAMPLE_SOLID_ANGLE_ALL samples sphere lights exactly as
+ * RT_LIGHT_SAMPLE_SOLID_ANGLE does, and a rect light by a uniform direction of the spherical rectangle it subtends
+ * from the vertex (Urena, Fajardo and King 2013, "An area-preserving parametrization for spherical rectangles"), so
+ * the rect's estimator has no cy / d2 factor either.  Modes 0 and 1 keep every bit of their behaviour.  "Rects only"
+ * is not offered: the value 2 is not a mode and stays RT_E_INVALID, like every other value.
+ *
+ * IEEE binary64 throughout; + - * /, a correctly rounded sqrt, comparisons and selects, in the order written (no
+ * fused multiply-add), and three functions sin, cos and acos that are NOT a libm's: they are pl_sin, pl_acos
+ * (csrc/rt/portable_libm.h; pl_acos through pl_atan2) and pl_cos (csrc/rt/portable_trig.h: pl_sin's reduction and
+ * its two polynomial kernels, in the cosine's quadrant order), each a fixed sequence of such operations and rint
+ * (round to nearest, ties to even), so a restatement gives the same bits.  pi = 3.141592653589793,
+ * twopi = 6.283185307179586.
+ * Light sample of a listed rect at a vertex (x, n), after the pick's draw D.  (d1, d2, axis) are the rect's two
+ * in-plane axes and its normal axis as in rt_render_direct; the rect is axis-aligned, so the local frame is this
+ * permutation of the coordinates and nothing is normalised.
+ *   x0 = d1_min - x[d1];  x1 = d1_max - x[d1];  y0 = d2_min - x[d2];  y1 = d2_max - x[d2];  z0 = offset - x[axis]
+ *   coplanar   z0 == 0: the sample contributes 0, consumes no further draw and traces no ray; it still counts as
+ *              taken.
+ *   flip       if z0 > 0: z0 = -z0, and w[axis] below is -z0 in place of z0.
+ *   zz = z0*z0
+ *   b0 = -y0 / sqrt(zz + y0*y0);  n1z = x1 / sqrt(zz + x1*x1);  b1 = y1 / sqrt(zz + y1*y1);
+ *   n3z = -x0 / sqrt(zz + x0*x0)                      (the z components of the four side planes' unit normals)
+ *   g0 = acos(-(b0 * n1z));  g1 = acos(-(n1z * b1));  g2 = acos(-(b1 * n3z));  g3 = acos(-(n3z * b0))
+ *   k = (twopi - g2) - g3;  S = (g0 + g1) - k                               (S: the rect's solid angle)
+ *   u = draw D+1;  v = draw D+2   (two draws exactly, as for the area form, whichever of the two cases follows)
+ *   small      !(S >= 2^-20) (a NaN too): the sample is the AREA form's on u and v, with rt_render_direct's /
+ *              rt_render_nee's own value text (y[d1] = d1_min + u * (d1_max - d1_min), ...; w = y - x).  The four
+ *              acos carry an absolute error of order 2^-50, so above the bound S is good to about 2^-30 relative,
+ *              a bias far below any frame's noise; below it the rect is so small in the vertex's sky that the
+ *              area form has no tail to remove.
+ *   otherwise  au = u * S + k
+ *              fu = (cos(au) * b0 - b1) / sin(au)
+ *              cu = 1.0 / sqrt(fu*fu + b0*b0);  cu = fu > 0 ? cu : -cu;  cu = cu < -1 ? -1 : cu > 1 ? 1 : cu
+ *              xu = -(cu * z0) / sqrt(1.0 - cu*cu);  xu = xu < x0 ? x0 : xu > x1 ? x1 : xu
+ *              dd = xu*xu + z0*z0;  d = sqrt(dd)
+ *              h0 = y0 / sqrt(dd + y0*y0);  h1 = y1 / sqrt(dd + y1*y1);  hv = h0 + v * (h1 - h0);  hv2 = hv*hv
+ *              yv = hv2 < 1.0 - 2^-40 ? (hv * d) / sqrt(1.0 - hv2) : y1
+ *              w[d1] = xu;  w[d2] = yv;  w[axis] = z0 (flip: -z0)
+ *   then as in rt_render_direct: d2 = len2(w); dist = sqrt(d2); cx = dot(n, w) / dist; cy = |w[axis]| / dist; the cut
+ *              !(cx > 0 && cy > 0) (a NaN from a degenerate division above is cut); the shadow ray (x, w) on
+ *              [0.001, 1 - 2^-20]; Le (FairyLight: colour * cy).
+ *   value      (not `small`)  RT_NEE_MIS clear and rt_render_direct:
+ *                g = cx * ((S * (double)L) / pi)                  grid pick: g = cx * ((S / p) / pi)
+ *              RT_NEE_MIS set:
+ *                gs = cx / pi;  pl = 1.0 / (S * (double)L)        grid pick: pl = p / S
+ *                g = gs / (pl + gs)
+ *              value_c = (a_c * Le_c) * g
+ * Emission weight (rt_render_nee): when the hit is a listed rect and the previous vertex took a sample, with o the
+ * origin of the segment's ray (the previous vertex): x0 ... S as above with o for x;
+ *   z0 == 0 or !(cx_prev > 0):  ws = 1;
+ *   else !(S >= 2^-20):     rt_render_nee's area-measure weight, unchanged (the light sample at o applied the same
+ *                           rule at the same point, so the two densities stay a consistent pair);
+ *   else RT_NEE_MIS set:    gs = cx_prev / pi;  pl as above, with p_j(cell_prev) under the grid pick;
+ *                           ws = gs / (pl + gs);
+ *   else RT_NEE_MIS clear:  ws = 0.
+ * Sphere lights and sphere hits keep the text above; everything else keeps rt_render_nee's.
+ * Why it is unbiased: (u, v) -> direction is area-preserving from the unit square times S onto the spherical
+ * rectangle, so the light sample's solid-angle density is 1 / S per pick (times 1 / L or p for the pick) over
+ * exactly the directions that meet the rect; the plain estimator is f cos / density = (a / pi) Le cx S / pick.  The
+ * Lambertian scatter's density is cx / pi per solid angle, and the weights are the balance heuristic in that
+ * measure at the previous vertex, as for the cone.  A coplanar vertex sees the rect edge-on (cy = 0 for every
+ * point of it), so nothing is lost there, and a scatter from it cannot hit the rect's face. */
+enum { RT_LIGHT_SAMPLE_SOLID_ANGLE_ALL = 3 };
+/* Sets how rt_render_direct / rt_render_nee sample the uploaded scene's lights until the next rt_scene_upload or
+ * rt_scene_light_sampling: RT_LIGHT_SAMPLE_AREA, RT_LIGHT_SAMPLE_SOLID_ANGLE (spheres) or
+ * RT_LIGHT_SAMPLE_SOLID_ANGLE_ALL (spheres and rects).  RT_E_INVALID: no uploaded scene, an unknown mode (the setting
+ * is then left as it was).  Blocks until work queued on the context's stream has finished. */
 int rt_scene_light_sampling(rt_ctx* ctx, int32_t mode);
 /* Test entry points like rt_light_pick_at: vertex i = (points[i], normals[i]) runs the whole light sample except
  * the shadow ray, on the path key (seed, pixel = i, sample = 0) from draw 0, with a = 1 and no emitter scaling.
  *   light     the light picked;  draws: the path's draw counter after the sample.
- *   flags     1: cut, !(cx > 0 && cy > 0);  2: inside (solid-angle mode).  g_plain = g_mis = 0 with either;
- *             inside also leaves w, cx and cy 0.
+ *   flags     1: cut, !(cx > 0 && cy > 0);  2: inside (a sphere by solid angle);  4: coplanar (a rect by solid
+ *             angle).  g_plain = g_mis = 0 with any of them; inside and coplanar also leave w, cx and cy 0.
+ *             8: small (a rect by solid angle whose sample is the area form's): a bit of its own that zeroes
+ *             nothing and may come with 1.
  *   g_plain   g with RT_NEE_MIS clear;  g_mis: g with it set.
  * rt_light_sample_at runs on the device under the scene's current pick and mode.  rt_light_sample_host is plain
  * C++ without a device, compiled without contraction, and takes the pick (cells: 0 uniform, 1 ... 64 the grid)

@@ -31,6 +31,7 @@
 // --light-grid N (with --nee or --direct): the spatially weighted light pick (rt_scene_light_pick) with N cells,
 // 1 ... 64, along the light grid's longest axis; 0, the default, is the uniform pick.
 // --light-cone (with --nee or --direct): sphere lights are sampled by solid angle (rt_scene_light_sampling).
+// --light-solid-angle (with --nee or --direct): sphere and rect lights are (also when --light-cone is given too).
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -69,6 +70,7 @@ struct Args {
   int light_grid = 0;  // --light-grid N: the light pick of --nee / --direct (0: uniform)
   bool light_grid_given = false;
   bool light_cone = false;  // --light-cone: solid-angle sampling of sphere lights in --nee / --direct
+  bool light_solid_angle = false;  // --light-solid-angle: ... of sphere and rect lights
   double fov = 20.0, focal = 1.0, aperture = 0.001;
   bool night = false, single_threaded = false;
   unsigned long long seed = 0x5EED;
@@ -90,7 +92,8 @@ struct Args {
                "         --direct --direct-chain K\n"
                "         --nee --nee-mis 0|1\n"
                "         --light-grid N (with --nee or --direct; 0 ... 64 cells, 0 = uniform pick)\n"
-               "         --light-cone (with --nee or --direct: sphere lights sampled by solid angle)\n");
+               "         --light-cone (with --nee or --direct: sphere lights sampled by solid angle)\n"
+               "         --light-solid-angle (with --nee or --direct: sphere and rect lights sampled by solid angle)\n");
   std::exit(2);
 }
 
@@ -375,8 +378,11 @@ int render_scene(const Args& a, const rt_scene_desc* desc, const rt_camera& cam)
     rt_destroy(ctx);
     return 1;
   }
-  if ((a.direct || a.nee) && a.light_cone && (st = rt_scene_light_sampling(ctx, RT_LIGHT_SAMPLE_SOLID_ANGLE))) {
-    std::fprintf(stderr, "error: --light-cone: %s\n", rt_last_error(ctx));
+  if ((a.direct || a.nee) && (a.light_cone || a.light_solid_angle) &&
+      (st = rt_scene_light_sampling(ctx, a.light_solid_angle ? (int32_t)RT_LIGHT_SAMPLE_SOLID_ANGLE_ALL
+                                                             : (int32_t)RT_LIGHT_SAMPLE_SOLID_ANGLE))) {
+    std::fprintf(stderr, "error: %s: %s\n", a.light_solid_angle ? "--light-solid-angle" : "--light-cone",
+                 rt_last_error(ctx));
     rt_destroy(ctx);
     return 1;
   }
@@ -620,6 +626,7 @@ int main(int argc, char** argv) {
       a.light_grid_given = true;
     }
     else if (s == "--light-cone") a.light_cone = true;
+    else if (s == "--light-solid-angle") a.light_solid_angle = true;
     else if (s == "--partition") {
       const std::string v = next();
       if (v == "tiles") a.partition = RT_PARTITION_TILES;
@@ -675,6 +682,8 @@ int main(int argc, char** argv) {
   if (a.direct_chain < 0) usage("--direct-chain K >= 0");
 
   if (a.light_cone && !(a.nee || a.direct)) usage("--light-cone sets the light sampling of --nee or --direct");
+  if (a.light_solid_angle && !(a.nee || a.direct))
+    usage("--light-solid-angle sets the light sampling of --nee or --direct");
   if (a.light_grid_given && !(a.nee || a.direct)) usage("--light-grid sets the light pick of --nee or --direct");
   if (a.light_grid < 0 || a.light_grid > 64) usage("--light-grid N in 0 ... 64");
 

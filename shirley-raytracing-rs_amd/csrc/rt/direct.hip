@@ -10,7 +10,8 @@
 // size and launch are the frame's (pass_frame.h); the kernel spells the frame's device pieces out, because with
 // any of them it runs 0.5 % slower on the night frame (profiles/passframe/direct_pieces.json).
 // Reference scenes only (no book-2 records): EXT = false instances.
-// A kSampleCone instance (light_cone.h) samples sphere lights by solid angle.
+// A kSampleCone instance (light_cone.h) samples sphere lights by solid angle, a kSampleAll instance
+// (light_rect.h) rect lights too.
 // light_pick_kernel (rt_light_pick_at) runs the grid's pick alone, one point per lane; light_sample_kernel
 // (rt_light_sample_at) the whole light sample but its shadow ray.
 #include <hip/hip_runtime.h>
@@ -142,9 +143,10 @@ __global__ __launch_bounds__(THREADS) void direct_kernel(DScene S, DCamera C, ui
 }
 
 // rt_render_direct
-// rt_render_direct; `grid` (null: the uniform pick) is read only where n_lights > 0; `cone`: the kSampleCone instances
+// rt_render_direct; `grid` (null: the uniform pick) is read only where n_lights > 0; `sample`: kSampleArea,
+// kSampleCone or kSampleAll, the instances' sample kind
 hipError_t launch_direct(const DScene& S, bool wide, const DCamera& C, uint64_t seed, int s_begin, int s_end, int chain,
-                         const DLight* lights, int n_lights, const DLightGrid* grid, bool cone, double* emission,
+                         const DLight* lights, int n_lights, const DLightGrid* grid, int sample, double* emission,
                          double* direct, hipStream_t stream) {
   if (S.exts) return hipErrorInvalidValue;  // (the caller refuses book-2 scenes)
   if (n_lights > 0 && !lights) return hipErrorInvalidValue;
@@ -156,7 +158,10 @@ hipError_t launch_direct(const DScene& S, bool wide, const DCamera& C, uint64_t 
       return launch_block(kernel, G.blocks(T), T, block_lds_bytes<M>(S, node4_bytes(false), T), stream, S, C, seed,
                           s_begin, s_end, chain, G.tiles_x, G.n_tiles, lights, n_lights, emission, direct, g);
     };
-    if (cone)
+    if (sample == kSampleAll)
+      return grid && n_lights > 0 ? go(direct_kernel<T, M, kPickGrid, kSampleAll>, *grid)
+                                  : go(direct_kernel<T, M, kPickUniform, kSampleAll>, NoLightGrid{});
+    if (sample == kSampleCone)
       return grid && n_lights > 0 ? go(direct_kernel<T, M, kPickGrid, kSampleCone>, *grid)
                                   : go(direct_kernel<T, M, kPickUniform, kSampleCone>, NoLightGrid{});
     return grid && n_lights > 0 ? go(direct_kernel<T, M, kPickGrid, kSampleArea>, *grid)
@@ -214,12 +219,13 @@ __global__ __launch_bounds__(kHitThreads) void light_sample_kernel(const DLight*
   r.w[2] = s.w.z;
   r.cx = s.cx;
   r.cy = s.cy;
-  r.g_plain = s.flags ? 0.0 : light_sample_g<false, PICK, SAMPLE>(lights[s.li], s, (double)n_lights);
-  r.g_mis = s.flags ? 0.0 : light_sample_g<true, PICK, SAMPLE>(lights[s.li], s, (double)n_lights);
+  const bool zero = SAMPLE == kSampleAll ? (s.flags & kLightZero) != 0 : s.flags != 0;
+  r.g_plain = zero ? 0.0 : light_sample_g<false, PICK, SAMPLE>(lights[s.li], s, (double)n_lights);
+  r.g_mis = zero ? 0.0 : light_sample_g<true, PICK, SAMPLE>(lights[s.li], s, (double)n_lights);
   out[i] = r;
 }
 
-hipError_t launch_light_sample(const DLight* lights, int n_lights, const DLightGrid* grid, bool cone, uint64_t seed,
+hipError_t launch_light_sample(const DLight* lights, int n_lights, const DLightGrid* grid, int sample, uint64_t seed,
                                int n, const double* points, const double* normals, rt_light_sample* out,
                                hipStream_t stream) {
   if (n <= 0) return hipSuccess;
@@ -228,7 +234,10 @@ hipError_t launch_light_sample(const DLight* lights, int n_lights, const DLightG
     return launch_block(kernel, (n + kHitThreads - 1) / kHitThreads, kHitThreads, 0, stream, lights, n_lights, seed, n,
                         points, normals, out, g);
   };
-  if (cone)
+  if (sample == kSampleAll)
+    return grid ? go(light_sample_kernel<kPickGrid, kSampleAll>, *grid)
+                : go(light_sample_kernel<kPickUniform, kSampleAll>, NoLightGrid{});
+  if (sample == kSampleCone)
     return grid ? go(light_sample_kernel<kPickGrid, kSampleCone>, *grid)
                 : go(light_sample_kernel<kPickUniform, kSampleCone>, NoLightGrid{});
   return grid ? go(light_sample_kernel<kPickGrid, kSampleArea>, *grid)

@@ -15,7 +15,8 @@
 // light grid of a kPickGrid instance (light_pick.h, DESIGN.md §18: the last argument, an empty record in the
 // uniform instances), whose path state holds one more integer: the cell of the vertex that took the light sample.
 // A kSampleCone instance (light_cone.h, DESIGN.md §19: rt_scene_light_sampling) samples sphere lights by solid
-// angle and weights a listed sphere hit from the cone that sphere subtends at the segment's origin.
+// angle and weights a listed sphere hit from the cone that sphere subtends at the segment's origin.  A kSampleAll
+// instance (light_rect.h) does that and treats rects alike, by the spherical rectangle they subtend.
 #include <hip/hip_runtime.h>
 
 #include "direct.h"
@@ -106,7 +107,7 @@ __global__ __launch_bounds__(THREADS) void nee_kernel(DScene S, DCamera C, uint6
         done = true;
       } else {
         const v3 din = d;  // the segment's direction (shade_factor replaces the ray)
-        const v3 oin = o;  // ... and its origin, the previous vertex (read by a kSampleCone instance only)
+        const v3 oin = o;  // ... and its origin, the previous vertex (read by the solid-angle instances only)
         bool has_emit = false;
         v3 mul = V(1.0, 1.0, 1.0), emit = V(0.0, 0.0, 0.0);
         const bool alive = shade_factor(S, S.texs, S.mats[mat], leaf, pn, rs, un, rng, o, d, h, prim, face, mul, emit,
@@ -115,7 +116,36 @@ __global__ __launch_bounds__(THREADS) void nee_kernel(DScene S, DCamera C, uint6
           double ws = 1.0;
           const int lj = prev ? prim_light[prim] : -1;
           if (lj >= 0 && (lights[lj].geometry != RT_GEOM_SPHERE || h.front_face)) {
-            if (SAMPLE == kSampleCone && lights[lj].geometry == RT_GEOM_SPHERE) {
+            // kSampleAll, a rect: its spherical rectangle at the previous vertex by the light sample's own rule
+            // (kRectSmall: the area-measure weight below; kRectCoplanar, or !(cx_prev > 0): ws stays 1)
+            int rect_w = kRectSmall;
+            double rect_S = 0.0;
+            if constexpr (SAMPLE == kSampleAll) {
+              const DLight& Lj = lights[lj];
+              const int gj = Lj.geometry;
+              if (gj != RT_GEOM_SPHERE) {
+                RectView rv;
+                rect_w = rect_open(Lj.p, gj == RT_GEOM_RECT_YZ ? oin.y : oin.x, gj == RT_GEOM_RECT_XY ? oin.y : oin.z,
+                                   gj == RT_GEOM_RECT_XY ? oin.z : gj == RT_GEOM_RECT_YZ ? oin.x : oin.y, rv);
+                if (!(cx_prev > 0.0)) rect_w = kRectCoplanar;
+                if (rect_w == kRectOpen) rect_S = rv.S;
+              }
+            }
+            if (SAMPLE == kSampleAll && rect_w != kRectSmall) {
+              if (rect_w == kRectOpen) {
+                if (MIS) {
+                  const double gs = cx_prev / kDirectPi;
+                  double pl;
+                  if constexpr (PICK == kPickGrid)
+                    pl = light_prob(grid, cell_prev, n_lights, lj) / rect_S;
+                  else
+                    pl = 1.0 / (rect_S * (double)n_lights);
+                  ws = gs / (pl + gs);
+                } else {
+                  ws = 0.0;
+                }
+              }
+            } else if (SAMPLE != kSampleArea && lights[lj].geometry == RT_GEOM_SPHERE) {
               // both densities per solid angle at the previous vertex: the scatter's cx_prev / pi, the light
               // sample's 1 / (2 pi om) per pick; from inside the sphere the light sample gave nothing
               const DLight& Lj = lights[lj];
@@ -186,9 +216,10 @@ __global__ __launch_bounds__(THREADS) void nee_kernel(DScene S, DCamera C, uint6
   accum[p * 3 + 2] = sum.z;
 }
 
-// rt_render_nee; `grid` (null: the uniform pick) is read only where n_lights > 0; `cone`: the kSampleCone instances
+// rt_render_nee; `grid` (null: the uniform pick) is read only where n_lights > 0; `sample`: kSampleArea, kSampleCone
+// or kSampleAll, the instances' sample kind
 hipError_t launch_nee(const DScene& S, bool wide, bool mis, const DCamera& C, uint64_t seed, int s_begin, int s_end,
-                      int max_depth, const DLight* lights, int n_lights, const DLightGrid* grid, bool cone,
+                      int max_depth, const DLight* lights, int n_lights, const DLightGrid* grid, int sample,
                       const int32_t* prim_light, double* accum, hipStream_t stream) {
   if (S.exts) return hipErrorInvalidValue;  // (the caller refuses book-2 scenes)
   if (!accum || !prim_light || (n_lights > 0 && !lights)) return hipErrorInvalidValue;
@@ -200,15 +231,17 @@ hipError_t launch_nee(const DScene& S, bool wide, bool mis, const DCamera& C, ui
       return launch_block(kernel, G.blocks(T), T, block_lds_bytes<M>(S, node4_bytes(false), T), stream, S, C, seed,
                           s_begin, s_end, max_depth, G.tiles_x, G.n_tiles, lights, n_lights, prim_light, accum, g);
     };
-    auto pick = [&](auto sample) {
-      constexpr int SM = decltype(sample)::value;
+    auto pick = [&](auto kind) {
+      constexpr int SM = decltype(kind)::value;
       if (grid && n_lights > 0)
         return mis ? go(nee_kernel<T, M, true, kPickGrid, SM>, *grid)
                    : go(nee_kernel<T, M, false, kPickGrid, SM>, *grid);
       return mis ? go(nee_kernel<T, M, true, kPickUniform, SM>, NoLightGrid{})
                  : go(nee_kernel<T, M, false, kPickUniform, SM>, NoLightGrid{});
     };
-    return cone ? pick(std::integral_constant<int, kSampleCone>{}) : pick(std::integral_constant<int, kSampleArea>{});
+    return sample == kSampleAll    ? pick(std::integral_constant<int, kSampleAll>{})
+           : sample == kSampleCone ? pick(std::integral_constant<int, kSampleCone>{})
+                                   : pick(std::integral_constant<int, kSampleArea>{});
   });
 }
 

@@ -60,7 +60,7 @@ struct rt_ctx {
   DevBuf light_cdf;
   rt::DLightGrid light_grid{};
   rt_light_grid light_grid_info{};
-  int32_t light_sampling = RT_LIGHT_SAMPLE_AREA;  // rt_scene_light_sampling: how the passes sample a sphere light
+  int32_t light_sampling = RT_LIGHT_SAMPLE_AREA;  // rt_scene_light_sampling: how the passes sample a light
   int32_t n_unlisted_lights = 0;
   rt_scene_stats stats{};
   int blocks_per_cu = 0;
@@ -182,8 +182,9 @@ inline int check_single_rank(rt_ctx* c, const rt_render_params* p, const char* n
 inline const DLightGrid* pass_light_grid(const rt_ctx* c) {
   return c->light_cells > 0 && !c->light_list.empty() ? &c->light_grid : nullptr;
 }
-// ... and whether they run their solid-angle instances (rt_scene_light_sampling).
-inline bool pass_light_cone(const rt_ctx* c) { return c->light_sampling == RT_LIGHT_SAMPLE_SOLID_ANGLE; }
+// ... and their instances' sample kind (rt_scene_light_sampling: the mode's value is kSampleArea, kSampleCone or
+// kSampleAll of light_cone.h / light_rect.h).
+inline int pass_light_sample(const rt_ctx* c) { return c->light_sampling; }
 inline int pass_check(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, const char* name) {
   const int st = check_render_args(c, cam, p);
   return st ? st : check_single_rank(c, p, name);

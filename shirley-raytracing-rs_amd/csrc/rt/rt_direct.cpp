@@ -43,7 +43,7 @@ int rt_render_direct_device(rt_ctx* c, const rt_camera* cam, const rt_render_par
   const int n_lights = (int)c->light_list.size();
   HIP_TRY(c, launch_direct(c->scene, c->place.wide, device_camera(cam), p->seed, R.begin, R.end, chain,
                            n_lights ? static_cast<const DLight*>(c->lights.p) : nullptr, n_lights,
-                           pass_light_grid(c), pass_light_cone(c), emission_dev, direct_dev, s));
+                           pass_light_grid(c), pass_light_sample(c), emission_dev, direct_dev, s));
   return RT_OK;
 }
 

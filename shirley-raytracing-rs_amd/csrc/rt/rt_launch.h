@@ -55,16 +55,16 @@ hipError_t launch_ao(const DScene& S, bool wide, const DCamera& C, uint64_t seed
                      double radius, double* ao, hipStream_t stream);
 // direct.hip
 hipError_t launch_direct(const DScene& S, bool wide, const DCamera& C, uint64_t seed, int s_begin, int s_end, int chain,
-                         const DLight* lights, int n_lights, const DLightGrid* grid, bool cone, double* emission,
+                         const DLight* lights, int n_lights, const DLightGrid* grid, int sample, double* emission,
                          double* direct, hipStream_t stream);
 hipError_t launch_light_pick(const DLightGrid& grid, int n_lights, int n, const double* points, const double* xi,
                              int32_t* light, double* prob, hipStream_t stream);
-hipError_t launch_light_sample(const DLight* lights, int n_lights, const DLightGrid* grid, bool cone, uint64_t seed,
+hipError_t launch_light_sample(const DLight* lights, int n_lights, const DLightGrid* grid, int sample, uint64_t seed,
                                int n, const double* points, const double* normals, rt_light_sample* out,
                                hipStream_t stream);
 // nee.hip
 hipError_t launch_nee(const DScene& S, bool wide, bool mis, const DCamera& C, uint64_t seed, int s_begin, int s_end,
-                      int max_depth, const DLight* lights, int n_lights, const DLightGrid* grid, bool cone,
+                      int max_depth, const DLight* lights, int n_lights, const DLightGrid* grid, int sample,
                       const int32_t* prim_light, double* accum, hipStream_t stream);
 // trace_split.hip
 bool split_supported_nt(int nt);

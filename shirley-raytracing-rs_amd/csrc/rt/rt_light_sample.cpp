@@ -1,14 +1,19 @@
-// rt_light_sample.cpp — solid-angle sampling of sphere lights in include/shirley_rt.h (added within ABI 11;
-// light_cone.h, direct.h, nee.hip, direct.hip's light_sample_kernel): the scene setting, the device
-// probe of one light sample per vertex, and the same sample in plain C++ without a device.
+// rt_light_sample.cpp — solid-angle sampling of sphere and rect lights in include/shirley_rt.h (added within ABI 11;
+// light_cone.h, light_rect.h, direct.h, nee.hip, direct.hip's light_sample_kernel): the scene
+// setting, the device probe of one light sample per vertex, and the same sample in plain C++ without a device.
 #include "rt_ctx.h"
 #include "light_cone.h"
+#include "light_rect.h"
 
 using namespace rt;
 
 namespace {
 
 constexpr double kPi = 3.141592653589793;
+// (the launchers take the mode's value as their instances' sample kind)
+static_assert(kSampleArea == RT_LIGHT_SAMPLE_AREA && kSampleCone == RT_LIGHT_SAMPLE_SOLID_ANGLE &&
+                  kSampleAll == RT_LIGHT_SAMPLE_SOLID_ANGLE_ALL,
+              "sample kinds are the public modes");
 
 // The path's draw `draw` of (seed, pixel, sample): Philox4x32-10 at counter (draw / 2, sample, pixel, 0), the low
 // word pair for an even draw and the high pair for an odd one, converted as (u64 >> 11) * 2^-53 (rt_device.h).
@@ -53,7 +58,7 @@ int host_grid_pick(const LightGridTable& t, const double* x, double xi, double* 
 double dot3(const double* a, const double* b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
 
 // One vertex of rt_light_sample_host: the header's light sample up to the shadow ray, with a = 1.
-void host_light_sample(const std::vector<DLight>& lights, const LightGridTable* grid, bool cone, uint64_t seed,
+void host_light_sample(const std::vector<DLight>& lights, const LightGridTable* grid, int mode, uint64_t seed,
                        uint32_t pixel, const double* x, const double* n, rt_light_sample* out) {
   const int L = (int)lights.size();
   const double nl = (double)L;
@@ -69,11 +74,34 @@ void host_light_sample(const std::vector<DLight>& lights, const LightGridTable* 
   }
   const DLight& Lt = lights[li];
   const int geom = Lt.geometry;
-  const bool solid_angle = cone && geom == RT_GEOM_SPHERE;
+  const bool solid_angle = mode != RT_LIGHT_SAMPLE_AREA && geom == RT_GEOM_SPHERE;
+  bool rect_angle = false;  // a rect's sample came from its spherical rectangle, of solid angle om
   rt_light_sample r{};
   r.light = li;
   double w[3], u[3] = {0.0, 0.0, 0.0}, om = 0.0;
-  if (solid_angle) {
+  if (mode == RT_LIGHT_SAMPLE_SOLID_ANGLE_ALL && geom != RT_GEOM_SPHERE) {
+    const int d1 = geom == RT_GEOM_RECT_YZ ? 1 : 0, d2 = geom == RT_GEOM_RECT_XY ? 1 : 2, ax = 3 - d1 - d2;
+    RectView rv;
+    const int open = rect_open(Lt.p, x[d1], x[d2], x[ax], rv);
+    if (open == kRectCoplanar) {
+      r.flags = 4;
+      r.draws = draw;
+      *out = r;
+      return;
+    }
+    const double xi1 = next();
+    const double xi2 = next();
+    if (open == kRectOpen) {
+      rect_angle = true;
+      om = rv.S;
+      rect_sample(rv, xi1, xi2, w[d1], w[d2], w[ax]);
+    } else {  // the area form's point on the same two draws
+      r.flags = 8;
+      w[d1] = (Lt.p[0] + xi1 * (Lt.p[1] - Lt.p[0])) - x[d1];
+      w[d2] = (Lt.p[2] + xi2 * (Lt.p[3] - Lt.p[2])) - x[d2];
+      w[ax] = Lt.p[4] - x[ax];
+    }
+  } else if (solid_angle) {
     const c3 c{Lt.p[0], Lt.p[1], Lt.p[2]}, xv{x[0], x[1], x[2]};
     c3 wc, cw, cu;
     double dc2;
@@ -132,7 +160,12 @@ void host_light_sample(const std::vector<DLight>& lights, const LightGridTable* 
   r.cx = cx;
   r.cy = cy;
   if (!(cx > 0.0 && cy > 0.0)) {
-    r.flags = 1;
+    r.flags |= 1;
+  } else if (rect_angle) {
+    r.g_plain = cx * ((grid ? om / pk : om * nl) / kPi);
+    const double gs = cx / kPi;
+    const double pl = grid ? pk / om : 1.0 / (om * nl);
+    r.g_mis = gs / (pl + gs);
   } else if (solid_angle) {
     r.g_plain = cx * (grid ? (2.0 * om) / pk : (2.0 * om) * nl);
     const double gs = cx / kPi;
@@ -147,7 +180,9 @@ void host_light_sample(const std::vector<DLight>& lights, const LightGridTable* 
   *out = r;
 }
 
-bool known_mode(int32_t mode) { return mode == RT_LIGHT_SAMPLE_AREA || mode == RT_LIGHT_SAMPLE_SOLID_ANGLE; }
+bool known_mode(int32_t mode) {
+  return mode == RT_LIGHT_SAMPLE_AREA || mode == RT_LIGHT_SAMPLE_SOLID_ANGLE || mode == RT_LIGHT_SAMPLE_SOLID_ANGLE_ALL;
+}
 
 }  // namespace
 
@@ -183,7 +218,7 @@ int rt_light_sample_at(rt_ctx* c, int32_t n, const double* points, const double*
     if (e == hipSuccess) e = hipMemcpyAsync(dn, normals, nd * 3 * sizeof(double), hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess)
       e = launch_light_sample(static_cast<const DLight*>(c->lights.p), (int)c->light_list.size(), pass_light_grid(c),
-                              pass_light_cone(c), seed, n, dp, dn, dout, c->stream);
+                              pass_light_sample(c), seed, n, dp, dn, dout, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(out, dout, nd * sizeof(rt_light_sample), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) st = fail(c, RT_E_HIP, "rt_light_sample_at: %s", hipGetErrorString(e));
@@ -201,7 +236,7 @@ int rt_light_sample_host(const rt_scene_desc* d, int32_t cells, int32_t mode, in
   LightGridTable t;
   if (cells > 0 && build_light_grid(l, cells, true, &t)) return RT_E_INVALID;
   for (int32_t i = 0; i < n; ++i)
-    host_light_sample(l.dev, cells > 0 ? &t : nullptr, mode == RT_LIGHT_SAMPLE_SOLID_ANGLE, seed, (uint32_t)i,
+    host_light_sample(l.dev, cells > 0 ? &t : nullptr, mode, seed, (uint32_t)i,
                       points + (size_t)i * 3, normals + (size_t)i * 3, out + i);
   return RT_OK;
 }

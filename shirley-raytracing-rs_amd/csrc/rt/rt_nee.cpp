@@ -24,7 +24,7 @@ int rt_render_nee_device(rt_ctx* c, const rt_camera* cam, const rt_render_params
   const int n_lights = (int)c->light_list.size();
   HIP_TRY(c, launch_nee(c->scene, c->place.wide, (flags & RT_NEE_MIS) != 0, device_camera(cam), p->seed, R.begin, R.end,
                         p->max_depth, n_lights ? static_cast<const DLight*>(c->lights.p) : nullptr, n_lights,
-                        pass_light_grid(c), pass_light_cone(c), static_cast<const int32_t*>(c->prim_light.p), accum_dev,
+                        pass_light_grid(c), pass_light_sample(c), static_cast<const int32_t*>(c->prim_light.p), accum_dev,
                         s));
   return RT_OK;
 }

@@ -28,6 +28,7 @@ RT_TRAVERSAL_BINARY, RT_TRAVERSAL_RENDER = 0, 1
 RT_PARTITION_AUTO, RT_PARTITION_TILES, RT_PARTITION_SAMPLES = 0, 1, 2
 RT_NEE_MIS = 1  # rt_render_nee flags
 RT_LIGHT_SAMPLE_AREA, RT_LIGHT_SAMPLE_SOLID_ANGLE = 0, 1  # rt_scene_light_sampling modes
+RT_LIGHT_SAMPLE_SOLID_ANGLE_ALL = 3  # ... spheres and rects by solid angle (2 is not a mode)
 
 _d3 = C.c_double * 3
 _d6 = C.c_double * 6

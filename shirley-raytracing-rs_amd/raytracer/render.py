@@ -400,9 +400,10 @@ class Device:
         return light[:len(p)], prob[:len(p)]
 
     def light_sampling(self, mode: int) -> None:
-        """rt_scene_light_sampling: how render_direct / render_nee sample a sphere light until the next upload():
-        N.RT_LIGHT_SAMPLE_AREA (a point of its area) or N.RT_LIGHT_SAMPLE_SOLID_ANGLE (a direction of the cone it
-        subtends from the vertex; include/shirley_rt.h).  Rect lights are sampled by area either way."""
+        """rt_scene_light_sampling: how render_direct / render_nee sample a light until the next upload():
+        N.RT_LIGHT_SAMPLE_AREA (a point of its area), N.RT_LIGHT_SAMPLE_SOLID_ANGLE (a sphere light: a direction of
+        the cone it subtends from the vertex; rects by area) or N.RT_LIGHT_SAMPLE_SOLID_ANGLE_ALL (that, and a rect
+        light: a direction of the spherical rectangle it subtends; include/shirley_rt.h)."""
         _check(self._h, N.rt_lib().rt_scene_light_sampling(self._h, int(mode)))
 
     def light_sample_at(self, points: np.ndarray, normals: np.ndarray, seed: int):
