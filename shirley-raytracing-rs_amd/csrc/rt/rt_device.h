@@ -1063,7 +1063,7 @@ __device__ __forceinline__ int traverse(const DScene& S, const DNode* lds_nodes,
 // per-lane step counter of the instrumented build (a register of the calling kernel)
 #define g_trav_lane_steps trav_lane_steps_ref
 // event counters of the instrumented build: slot 2i += active lanes, slot 2i + 1 += 1 (per wave)
-constexpr int kPhaseEvents = 52;
+constexpr int kPhaseEvents = 56;
 static __device__ unsigned long long g_phase_ctr[2 * kPhaseEvents];
 // histograms of the instrumented build: node visits per traversing lane, and per wave (its slowest lane)
 static __device__ unsigned long long g_visit_hist[64], g_wave_visit_hist[64];
@@ -2727,6 +2727,46 @@ __device__ __forceinline__ void shade_dielectric(const DMat& m, v3 r, v3 un, Rng
   }
   o = h.point;
   d = refl ? reflect(ud, h.normal) : refract(ud, h.normal, ratio);
+}
+// The hop passes' serve body — hit_record<false, false>, unit_fast, shade_dielectric — for a hit on a y face of a
+// RectBox (face 4 or 5), with the axis normal written out (the HOP = 4 instances; DESIGN.md §3.1 gives the argument
+// per expression).  The record's normal is (0, 1, 0) for a front face, d.y < 0, and (-0, -1, -0) otherwise, so every
+// product with its x or z component is a signed zero and every product with its y component the other factor or
+// its negation, exactly.  Adding a signed zero leaves a non-zero operand as it is: with every |d_i| >= 2^-300,
+// |d| <= 2^300 (unit_fast's own range test, so every |ud_i| >= 2^-601) and ratio >= 2^-400 (so ud_i ratio does not
+// underflow) each operand that meets such a zero is non-zero, and the reduced expressions give the general body's
+// bits.  Any other lane — a zero or tiny component, where the sign of a zero sum would depend on the dropped term —
+// returns false with nothing changed, and the caller runs the general body.  r: draw_diel's uniform, as for
+// shade_dielectric.
+__device__ __forceinline__ bool serve_y(const DMat& m, v3 r, Rng& rng, v3& o, v3& d, double t) {
+  const double n = len(d);
+  const double mn = fmin(fmin(fabs(d.x), fabs(d.y)), fabs(d.z));
+  const bool front = d.y < 0.0;  // dot(d, (0, 1, 0)) < 0
+  const double ratio = front ? m.inv_param : m.param;
+  if (!(mn >= 0x1p-300 && n <= 0x1p300 && ratio >= 0x1p-400)) return false;
+  PH_COUNT(17);
+  const Recip R = recip(n);
+  const v3 ud = V(div_recip(d.x, R), div_recip(d.y, R), div_recip(d.z, R));
+  const double cos_theta = fmin_one(fabs(ud.y));  // -ud.y n.y, and sign(ud.y) = sign(d.y) = -n.y
+  bool refl = ratio > 1.0 && ratio * sqrt_rn(1.0 - cos_theta * cos_theta) > 1.0;
+  if (!refl) {
+    PH_COUNT(22);
+    refl = reflectance_r0sq(cos_theta, front ? m.albedo[0] : m.albedo[1]) > r.x;
+    const uint64_t cb = double_as_u64(r.y);
+    rng.draw += 1u;
+    rng.c2 = (uint32_t)cb;
+    rng.c3 = (uint32_t)(cb >> 32);
+  }
+  o = o + scale(d, t);
+  if (refl) {
+    d = V(ud.x, -ud.y, ud.z);  // ud - n (2 ud.y n.y): y is ud.y - 2 ud.y, exact
+  } else {
+    const double px = ud.x * ratio, pz = ud.z * ratio;
+    const double py = ((front ? cos_theta : -cos_theta) + ud.y) * ratio;
+    const double mag = sqrt_rn(fabs(1.0 - len2(V(px, py, pz)))) * -1.0;
+    d = V(px, py + (front ? mag : -mag), pz);
+  }
+  return true;
 }
 // shade_pre<true> with the path's attenuation and emission left to the caller, so that the megakernel
 // reads and writes them once per segment instead of once per material branch: the material's

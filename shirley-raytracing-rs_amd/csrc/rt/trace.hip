@@ -107,9 +107,10 @@ constexpr int kNarrowWaves = RT_NARROW_WAVES;
 #endif
 // HOP = 4 (HOP = 3 on a plane stack, ScenePlacement.hop_planes): the same two passes with plane_hop_t for the stack's
 // answer — no general ground_hop_t code in the instance.  Its own thresholds, re-swept with the cheaper run: the down
-// pass at 24 / 16 / 16 and step 5' at 16 / 8 (profiles/planehop/threshold_sweep.jsonl).
+// pass at 24 / 16 / 16 and step 5' at 16 / 8 (profiles/planehop/threshold_sweep.jsonl), and the down
+// pass's first run at 20 with serve_y's cheaper serve body (RT_SERVE_Y below; profiles/servey/threshold_sweep.jsonl).
 #ifndef RT_HOP4D_MIN_LANES_A
-#define RT_HOP4D_MIN_LANES_A 24
+#define RT_HOP4D_MIN_LANES_A (RT_SERVE_Y ? 20 : 24)
 #endif
 #ifndef RT_HOP4D_MIN_LANES_B
 #define RT_HOP4D_MIN_LANES_B RT_HOPD_MIN_LANES_B
@@ -127,6 +128,11 @@ constexpr int kNarrowWaves = RT_NARROW_WAVES;
 // first visit (rt_device.h plane_first, traverse4 GF).  0 builds the A/B partner (tools/variant.sh).
 #ifndef RT_GROUND_FIRST
 #define RT_GROUND_FIRST 1
+#endif
+// ... and both passes shade a hit on a y face of a RectBox by the serve body written out for its axis normal
+// (rt_device.h serve_y).  0 builds the A/B partner with the general body alone (tools/variant.sh).
+#ifndef RT_SERVE_Y
+#define RT_SERVE_Y 1
 #endif
 #ifdef RT_HOP_SERVE_SHARED
 // A/B only: the serve body of the HOP = 3 instances as one call that the down pass and step 5' both
@@ -321,12 +327,28 @@ void trace_kernel(KParams P) {
           const ServeOut so = hop_serve_ool(lds_prims, mats, prim, face, o, d, t_best, rng, seed);
           o = so.o, d = so.d, rng.draw = so.draw, rng.c2 = so.c2, rng.c3 = so.c3;
 #else
+          if constexpr (HOP == 4 && RT_SERVE_Y) {
+            // (a y face — nearly every hit the traversal hands the pass — by serve_y; a side face, or a lane serve_y
+            // sends back, by the general body)
+            const DMat& dm = mats[lds_prims[prim].material];
+            const v3 ru = draw_diel(rng, seed);
+            const bool by_y = face >= 4 && serve_y(dm, ru, rng, o, d, t_best);
+            if (by_y) PH_COUNT(51);
+            if (!by_y) {
+              PH_COUNT(52);
+              const DPrim pr = lds_prims[prim];
+              Hit hh;
+              hit_record<false, false>(S, pr, face, o, d, t_best, rng, seed, hh);
+              shade_dielectric(dm, ru, unit_fast(d), rng, o, d, hh);
+            }
+          } else {
           const DPrim pr = lds_prims[prim];
           Hit hh;
           hit_record<false, false>(S, pr, face, o, d, t_best, rng, seed, hh);
           const v3 ru = draw_diel(rng, seed);
           const v3 ud = unit_fast(d);
           shade_dielectric(mats[pr.material], ru, ud, rng, o, d, hh);  // (att * 1 = att, no emission)
+          }
 #endif
           if (--depth_left <= 0) {
             sum = sum + em;
@@ -701,7 +723,19 @@ void trace_kernel(KParams P) {
             o = so.o, d = so.d, rng.draw = so.draw, rng.c2 = so.c2, rng.c3 = so.c3;
           } else
 #endif
-          {
+          if constexpr (HOP == 4 && RT_SERVE_Y) {  // (as in the down pass: every served hit of a plane stack is a y face)
+            const DMat& dm = mats[lds_prims[p_hop].material];
+            const v3 ru = draw_diel(rng, seed);
+            const bool by_y = f_hop >= 4 && serve_y(dm, ru, rng, o, d, t_hop);
+            if (by_y) PH_COUNT(53);
+            if (!by_y) {
+              PH_COUNT(54);
+              const DPrim pr = lds_prims[p_hop];
+              Hit hh;
+              hit_record<false, false>(S, pr, f_hop, o, d, t_hop, rng, seed, hh);
+              shade_dielectric(dm, ru, unit_fast(d), rng, o, d, hh);
+            }
+          } else {
           const DPrim pr = lds_prims[p_hop];
           Hit hh;
           hit_record<false, false>(S, pr, f_hop, o, d, t_hop, rng, seed, hh);
@@ -1382,7 +1416,9 @@ void phase_counters_dump() {
                                 "down3_try", "down3_served", "down3_found", "down3_wait",
                                 // ... and the lanes of each run that ask the stack (alive, running inward or down):
                                 // ask - served - found were refused (HOP = 4: declined)
-                                "down1_ask", "down2_ask", "down3_ask"};
+                                "down1_ask", "down2_ask", "down3_ask",
+                                // HOP = 4: the serve body's lanes by form, in the down pass and in step 5'
+                                "down_serve_y", "down_serve_general", "hop_serve_y", "hop_serve_general"};
   static_assert(sizeof names / sizeof names[0] <= kPhaseEvents, "event slots");
   for (int i = 0; i < (int)(sizeof names / sizeof names[0]); ++i)
     if (h[2 * i + 1])
