@@ -949,6 +949,74 @@ int rt_light_sample_at(rt_ctx* ctx, int32_t n, const double* points, const doubl
 int rt_light_sample_host(const rt_scene_desc* scene, int32_t cells, int32_t mode, int32_t n, const double* points,
                          const double* normals, uint64_t seed, rt_light_sample* out);
 
+/* ---- visibility-aware light pick: traced occlusion per cell -------------------------
+ * Added within ABI 11 like the light list: purely additive, RT_ABI_VERSION stays 11.
+ *
+ * A third scene-level setting, next to rt_scene_light_pick and rt_scene_light_sampling and independent of the
+ * sampling mode.  It traces K shadow rays from every cell of the grid last set by rt_scene_light_pick to every
+ * listed light and rebuilds every row with each light's weight multiplied by a smoothed share of the cell's points
+ * that see the light.  rt_render_direct, rt_render_nee and rt_light_pick_at read other numbers in the rows and
+ * nothing else.  rt_scene_upload and rt_scene_light_pick (any value) switch it off, so a caller that never sets it
+ * sees no change.
+ *
+ * IEEE binary64 throughout; only + - * /, a correctly rounded sqrt, comparisons and selects, in the order written
+ * (no fused multiply-add, no libm function).  rng(seed, pixel, sample, draw) is the counter RNG's draw: the
+ * device's rng_next on Rng{pixel, sample, draw}.  The grid, lo, size_a, cell_lo_a, w_j, the row rule (above) and
+ * the light record (rt_scene_lights) are as defined there.  Rays per pair: K in {1, 2, 4, 8, 16, 32}.
+ * For cell row c = (iz * n_y + iy) * n_x + ix, cell point i in [0, K), light j in [0, L):
+ *   cell point  x_a = cell_lo_a + rng(seed, c, i, a) * size_a for a = 0, 1, 2: shared by all lights of the cell.
+ *   target      rect: xi1 = rng(seed, c, i, 4 + 2j), xi2 = rng(seed, c, i, 5 + 2j); y by rt_render_direct's `rect`
+ *               rule (y[d1] = d1_min + xi1 * (d1_max - d1_min), y[d2] = d2_min + xi2 * (d2_max - d2_min),
+ *               y[axis] = offset).  The draws start at an even index; draw 3 is unused.
+ *               sphere (centre q, radius r): e = x - q;  e2 = (e.x*e.x + e.y*e.y) + e.z*e.z.
+ *               !(e2 > r*r): the pair's bit i is set and no ray is traced.  Otherwise le = sqrt(e2) and
+ *               y_a = q_a + r * (e_a / le): the light's nearest point, which is deterministic (the cone mode samples
+ *               that cap anyway).
+ *   ray         w = y - x;  w2 = (w.x*w.x + w.y*w.y) + w.z*w.z.  !(w2 > 0): the bit is set and no ray is traced.
+ *               Otherwise the bit is set iff (x, w) is not occluded on [0.001, 1 - 2^-20] in the sense of
+ *               rt_scene_occluded: the passes' shadow interval.
+ *   mask        mask[c][j] is a uint32 whose bit i is the above.
+ *   rows        per cell: valid = mask[c][0] | mask[c][1] | ...;  Kc = popcount(valid).  A point that no light sees
+ *               is dead: it lies inside an object, and every light's count skips it.
+ *               Kc == 0: the cell keeps rt_scene_light_pick's row.
+ *               otherwise u_j = popcount(mask[c][j]);  v_j = ((double)u_j + 1.0) / ((double)Kc + 2.0);
+ *               w'_j = w_j * v_j;  W' = ((0 + w'_0) + w'_1) + ... in list order; then the `row` rule above with w',
+ *               W' in place of w, W: the 0.875 / 0.125 split, the fallback for W' of 0, +inf or a NaN, and
+ *               cdf_(L-1) = 1.0 exactly.  (Bits of a mask at or above K are ignored.)
+ * Why it stays unbiased: every p_j >= 0.125 / L still; the table is fixed before any sample is drawn; the row
+ * depends on the vertex's cell alone; and the estimator and the MIS weights divide by the p of the same rows, which
+ * light_prob reads.  The bound "8 times the uniform pick's" on every estimate still holds.  A wrong mask costs
+ * variance, never expectation. */
+typedef struct rt_light_visibility {
+  int32_t rays, pad;    /* K; 0 when off */
+  uint64_t seed;
+  uint64_t pairs;       /* cells * L */
+  uint64_t traced;      /* shadow rays traced (bits decided without a ray are not counted) */
+  uint64_t unoccluded;  /* bits set */
+  uint64_t dead_points; /* cell points no light sees */
+  double kernel_ms;     /* device time of the trace kernel */
+} rt_light_visibility;
+/* Traces the masks of the uploaded scene in the grid last set by rt_scene_light_pick, builds the rows on the host
+ * and uploads them in place of the grid's, until the next rt_scene_upload, rt_scene_light_pick or
+ * rt_scene_light_visibility.  rays = 0 puts rt_scene_light_pick's rows back (RT_OK too when nothing was set).
+ * `report` (may be NULL) receives the counts (all zero for rays = 0).  RT_E_INVALID: no uploaded scene, rays not 0,
+ * 1, 2, 4, 8, 16 or 32, the uniform pick is set, the scene lists no light (the setting is then left as it was).
+ * RT_E_UNSUPPORTED: a scene with book-2 objects, like rt_scene_occluded.  Blocks, like rt_scene_light_pick. */
+int rt_scene_light_visibility(rt_ctx* ctx, int32_t rays, uint64_t seed, rt_light_visibility* report);
+/* Test entry point: the masks the device traced for the setting in force, [cells][L].  RT_E_INVALID: no uploaded
+ * scene, the setting is off, a NULL buffer. */
+int rt_light_visibility_masks(rt_ctx* ctx, uint32_t* masks);
+/* The K rays of one (cell, light) pair, without a device: rays_out [K][6] = x, w and traced [K] = 1 where the ray
+ * is traced, 0 where the bit is set without one (w is 0, 0, 0 from inside a sphere light).  RT_E_INVALID: a NULL
+ * or invalid scene, a NULL buffer, cells outside 1 ... 64, a table of more than 2^22 entries, rays not one of the six
+ * values, no listed light, cell or light out of range. */
+int rt_light_visibility_rays_host(const rt_scene_desc* scene, int32_t cells, int32_t rays, uint64_t seed, int32_t cell,
+                                  int32_t light, double* rays_out, uint8_t* traced);
+/* The rows for given masks ([cells][L]), without a device: cdf as rt_light_grid_host lays it out.  RT_E_INVALID: as
+ * above (no cell, light or seed here). */
+int rt_light_visibility_rows_host(const rt_scene_desc* scene, int32_t cells, int32_t rays, const uint32_t* masks,
+                                  double* cdf);
+
 #ifdef __cplusplus
 }
 #endif

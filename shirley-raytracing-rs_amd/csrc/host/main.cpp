@@ -30,6 +30,8 @@
 // the same restrictions as --direct, and not together with it.
 // --light-grid N (with --nee or --direct): the spatially weighted light pick (rt_scene_light_pick) with N cells,
 // 1 ... 64, along the light grid's longest axis; 0, the default, is the uniform pick.
+// --light-visibility K (with --light-grid N >= 1): K shadow rays per cell and light weight the grid's rows
+// (rt_scene_light_visibility); the seed is the render's.
 // --light-cone (with --nee or --direct): sphere lights are sampled by solid angle (rt_scene_light_sampling).
 // --light-solid-angle (with --nee or --direct): sphere and rect lights are (also when --light-cone is given too).
 #include <chrono>
@@ -69,6 +71,8 @@ struct Args {
   int nee_mis = 1;
   int light_grid = 0;  // --light-grid N: the light pick of --nee / --direct (0: uniform)
   bool light_grid_given = false;
+  int light_visibility = 0;  // --light-visibility K: shadow rays per (cell, light) of the grid (0: off)
+  bool light_visibility_given = false;
   bool light_cone = false;  // --light-cone: solid-angle sampling of sphere lights in --nee / --direct
   bool light_solid_angle = false;  // --light-solid-angle: ... of sphere and rect lights
   double fov = 20.0, focal = 1.0, aperture = 0.001;
@@ -92,6 +96,7 @@ struct Args {
                "         --direct --direct-chain K\n"
                "         --nee --nee-mis 0|1\n"
                "         --light-grid N (with --nee or --direct; 0 ... 64 cells, 0 = uniform pick)\n"
+               "         --light-visibility K (with --light-grid N >= 1: 1, 2, 4, 8, 16 or 32 shadow rays per cell and light)\n"
                "         --light-cone (with --nee or --direct: sphere lights sampled by solid angle)\n"
                "         --light-solid-angle (with --nee or --direct: sphere and rect lights sampled by solid angle)\n");
   std::exit(2);
@@ -378,6 +383,17 @@ int render_scene(const Args& a, const rt_scene_desc* desc, const rt_camera& cam)
     rt_destroy(ctx);
     return 1;
   }
+  if (a.light_visibility > 0) {  // (the argument checks left it with --light-grid N >= 1 and --nee / --direct)
+    rt_light_visibility rep;
+    if ((st = rt_scene_light_visibility(ctx, a.light_visibility, p.seed, &rep))) {
+      std::fprintf(stderr, "error: --light-visibility: %s\n", rt_last_error(ctx));
+      rt_destroy(ctx);
+      return 1;
+    }
+    std::fprintf(stderr, "light visibility: %llu shadow rays for %llu cell-light pairs in %.3f ms, %llu unoccluded\n",
+                 (unsigned long long)rep.traced, (unsigned long long)rep.pairs, rep.kernel_ms,
+                 (unsigned long long)rep.unoccluded);
+  }
   if ((a.direct || a.nee) && (a.light_cone || a.light_solid_angle) &&
       (st = rt_scene_light_sampling(ctx, a.light_solid_angle ? (int32_t)RT_LIGHT_SAMPLE_SOLID_ANGLE_ALL
                                                              : (int32_t)RT_LIGHT_SAMPLE_SOLID_ANGLE))) {
@@ -625,6 +641,10 @@ int main(int argc, char** argv) {
       a.light_grid = std::atoi(next().c_str());
       a.light_grid_given = true;
     }
+    else if (s == "--light-visibility") {
+      a.light_visibility = std::atoi(next().c_str());
+      a.light_visibility_given = true;
+    }
     else if (s == "--light-cone") a.light_cone = true;
     else if (s == "--light-solid-angle") a.light_solid_angle = true;
     else if (s == "--partition") {
@@ -686,6 +706,12 @@ int main(int argc, char** argv) {
     usage("--light-solid-angle sets the light sampling of --nee or --direct");
   if (a.light_grid_given && !(a.nee || a.direct)) usage("--light-grid sets the light pick of --nee or --direct");
   if (a.light_grid < 0 || a.light_grid > 64) usage("--light-grid N in 0 ... 64");
+  if (a.light_visibility_given) {
+    const int k = a.light_visibility;
+    if (!(k == 1 || k == 2 || k == 4 || k == 8 || k == 16 || k == 32)) usage("--light-visibility K in 1, 2, 4, 8, 16, 32");
+    if (!(a.nee || a.direct) || a.light_grid < 1)
+      usage("--light-visibility weights the grid of --light-grid N (N >= 1) with --nee or --direct");
+  }
 
   sh_scene* scene = nullptr;
   std::string cam_scene = a.scene;

@@ -505,7 +505,7 @@ int rt_destroy(rt_ctx* c) {
   if (!c) return RT_OK;
   (void)hipSetDevice(c->device);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
-  for (DevBuf* b : {&c->nodes, &c->nodes4, &c->prims, &c->mats, &c->texs, &c->perlin, &c->texels, &c->exts, &c->ground, &c->planes, &c->lights, &c->prim_light, &c->light_cdf, &c->partial, &c->kcam, &c->shutter0, &c->moments, &c->tile_list, &c->tile_err, &c->dn_a, &c->dn_b, &c->feat,
+  for (DevBuf* b : {&c->nodes, &c->nodes4, &c->prims, &c->mats, &c->texs, &c->perlin, &c->texels, &c->exts, &c->ground, &c->planes, &c->lights, &c->prim_light, &c->light_cdf, &c->light_vis_out, &c->partial, &c->kcam, &c->shutter0, &c->moments, &c->tile_list, &c->tile_err, &c->dn_a, &c->dn_b, &c->feat,
                     &c->accum, &c->counters, &c->unit_counter, &c->wf_pool, &c->wf_iters, &c->packed, &c->gathered,
                     &c->parts, &c->band, &c->digests})
     release(*b);
@@ -620,6 +620,8 @@ int rt_scene_upload(rt_ctx* c, const rt_scene_desc* d, int32_t builder) {
   c->light_dev = std::move(cs.lights.dev);
   c->light_cells = 0;  // every upload starts with the uniform pick (rt_scene_light_pick)
   c->light_sampling = RT_LIGHT_SAMPLE_AREA;  // ... and with area sampling (rt_scene_light_sampling)
+  c->light_vis = rt_light_visibility{};       // ... and without visibility weights (rt_scene_light_visibility)
+  c->light_vis_masks.clear();
   c->n_unlisted_lights = cs.lights.n_unlisted;
   c->stats = cs.stats;
   c->digest = cs.digest;

@@ -61,6 +61,12 @@ struct rt_ctx {
   rt::DLightGrid light_grid{};
   rt_light_grid light_grid_info{};
   int32_t light_sampling = RT_LIGHT_SAMPLE_AREA;  // rt_scene_light_sampling: how the passes sample a light
+  // rt_scene_light_visibility: the report of the setting in force (rays == 0: off, the rows are the plain grid's),
+  // the masks the device traced ([cells][L], kept for rt_light_visibility_masks) and the kernel's output buffer
+  // (the masks, then the per-wave counts of traced rays)
+  rt_light_visibility light_vis{};
+  std::vector<uint32_t> light_vis_masks;
+  DevBuf light_vis_out;
   int32_t n_unlisted_lights = 0;
   rt_scene_stats stats{};
   int blocks_per_cu = 0;

@@ -47,6 +47,8 @@ int rt_scene_light_pick(rt_ctx* c, int32_t cells, rt_light_grid* info) {
   c->light_grid = g;
   c->light_grid_info = t.info;
   c->light_cells = cells;
+  c->light_vis = rt_light_visibility{};  // the new rows are the plain grid's (rt_scene_light_visibility: off)
+  c->light_vis_masks.clear();
   if (info) *info = t.info;
   return RT_OK;
 }

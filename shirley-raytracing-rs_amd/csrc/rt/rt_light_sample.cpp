@@ -15,27 +15,6 @@ static_assert(kSampleArea == RT_LIGHT_SAMPLE_AREA && kSampleCone == RT_LIGHT_SAM
                   kSampleAll == RT_LIGHT_SAMPLE_SOLID_ANGLE_ALL,
               "sample kinds are the public modes");
 
-// The path's draw `draw` of (seed, pixel, sample): Philox4x32-10 at counter (draw / 2, sample, pixel, 0), the low
-// word pair for an even draw and the high pair for an odd one, converted as (u64 >> 11) * 2^-53 (rt_device.h).
-double path_draw(uint64_t seed, uint32_t pixel, uint32_t sample, uint32_t draw) {
-  uint32_t c[4] = {draw >> 1, sample, pixel, 0u};
-  uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-  for (int r = 0; r < 10; ++r) {
-    if (r) {
-      k0 += 0x9E3779B9u;
-      k1 += 0xBB67AE85u;
-    }
-    const uint64_t p0 = (uint64_t)0xD2511F53u * c[0], p1 = (uint64_t)0xCD9E8D57u * c[2];
-    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1;
-    c[0] = n0;
-    c[1] = (uint32_t)p1;
-    c[2] = n2;
-    c[3] = (uint32_t)p0;
-  }
-  const uint64_t v = (draw & 1u) ? ((uint64_t)c[2] | ((uint64_t)c[3] << 32)) : ((uint64_t)c[0] | ((uint64_t)c[1] << 32));
-  return (double)(v >> 11) * (1.0 / 9007199254740992.0);
-}
-
 // The grid pick of light_pick.h on the host table: the vertex's cell, the smallest k with xi < cdf_k, its p.
 int host_cell_axis(double x, double lo, double hi, int n) {
   const double inv = n == 1 ? 0.0 : (double)n / (hi - lo);

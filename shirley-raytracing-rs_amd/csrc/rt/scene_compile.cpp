@@ -986,7 +986,10 @@ LightList list_lights(const rt_scene_desc* d) {
 
 // The light grid of include/shirley_rt.h (rt_scene_light_pick), step by step in the header's order: + - * /,
 // comparisons and selects only (no libm; the build never fuses a * b + c).
-int build_light_grid(const LightList& l, int32_t cells, bool want_cdf, LightGridTable* out) {
+// With `masks` (rt_scene_light_visibility: [cells][L] words of `rays` bits each), a cell that has a live point
+// builds its row from w'_j = w_j * v_j, v_j the smoothed share of the cell's live points that see light j.
+int build_light_grid(const LightList& l, int32_t cells, bool want_cdf, LightGridTable* out, const uint32_t* masks,
+                     int32_t rays) {
   *out = LightGridTable{};
   if (cells < 1 || cells > kLightGridMaxCells) return RT_E_INVALID;
   const size_t L = l.dev.size();
@@ -1083,6 +1086,21 @@ int build_light_grid(const LightList& l, int32_t cells, bool want_cdf, LightGrid
           w[j] = it.phi / (D2 > m ? D2 : m);
           W = W + w[j];
         }
+        if (masks) {
+          const uint32_t field = rays >= 32 ? 0xFFFFFFFFu : (1u << rays) - 1u;
+          const uint32_t* m = masks + (size_t)(row - out->cdf.data());
+          uint32_t valid = 0;
+          for (size_t j = 0; j < L; ++j) valid |= m[j] & field;
+          const int Kc = __builtin_popcount(valid);  // the cell's live points: those some light sees
+          if (Kc) {
+            W = 0.0;
+            for (size_t j = 0; j < L; ++j) {
+              const double v = ((double)__builtin_popcount(m[j] & field) + 1.0) / ((double)Kc + 2.0);
+              w[j] = w[j] * v;
+              W = W + w[j];
+            }
+          }
+        }
         // (W is 0, +inf or a NaN: the uniform row)
         const bool weighted = W > 0.0 && W < std::numeric_limits<double>::infinity();
         double acc = 0.0;
@@ -1097,6 +1115,61 @@ int build_light_grid(const LightList& l, int32_t cells, bool want_cdf, LightGrid
         row[L - 1] = 1.0;
       }
   return RT_OK;
+}
+
+// The path's draw `draw` of (seed, pixel, sample): Philox4x32-10 at counter (draw / 2, sample, pixel, 0), the low
+// word pair for an even draw and the high pair for an odd one, converted as (u64 >> 11) * 2^-53 (rt_device.h).
+double path_draw(uint64_t seed, uint32_t pixel, uint32_t sample, uint32_t draw) {
+  uint32_t c[4] = {draw >> 1, sample, pixel, 0u};
+  uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+  for (int r = 0; r < 10; ++r) {
+    if (r) {
+      k0 += 0x9E3779B9u;
+      k1 += 0xBB67AE85u;
+    }
+    const uint64_t p0 = (uint64_t)0xD2511F53u * c[0], p1 = (uint64_t)0xCD9E8D57u * c[2];
+    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1;
+    c[0] = n0;
+    c[1] = (uint32_t)p1;
+    c[2] = n2;
+    c[3] = (uint32_t)p0;
+  }
+  const uint64_t v = (draw & 1u) ? ((uint64_t)c[2] | ((uint64_t)c[3] << 32)) : ((uint64_t)c[0] | ((uint64_t)c[1] << 32));
+  return (double)(v >> 11) * (1.0 / 9007199254740992.0);
+}
+
+// One ray of rt_scene_light_visibility in the header's order (lightvis.hip is the device's form).
+bool light_visibility_ray(const rt_light_grid& g, const DLight& q, uint64_t seed, uint32_t cell, uint32_t light,
+                          uint32_t i, double* x, double* w) {
+  const uint32_t nx = (uint32_t)g.n[0], ny = (uint32_t)g.n[1];
+  const uint32_t iz = cell / (nx * ny), iy = (cell - iz * (nx * ny)) / nx, ix = cell - (iz * ny + iy) * nx;
+  const uint32_t idx[3] = {ix, iy, iz};
+  for (int a = 0; a < 3; ++a) {
+    const double size = (g.hi[a] - g.lo[a]) / (double)g.n[a];
+    x[a] = (g.lo[a] + (double)idx[a] * size) + path_draw(seed, cell, i, (uint32_t)a) * size;
+  }
+  double y[3];
+  if (q.geometry == RT_GEOM_SPHERE) {
+    const double r = q.p[3];
+    const double e[3] = {x[0] - q.p[0], x[1] - q.p[1], x[2] - q.p[2]};
+    const double e2 = (e[0] * e[0] + e[1] * e[1]) + e[2] * e[2];
+    if (!(e2 > r * r)) {
+      w[0] = w[1] = w[2] = 0.0;
+      return false;
+    }
+    const double le = std::sqrt(e2);
+    for (int a = 0; a < 3; ++a) y[a] = q.p[a] + r * (e[a] / le);
+  } else {
+    const int d1 = q.geometry == RT_GEOM_RECT_YZ ? 1 : 0;
+    const int d2 = q.geometry == RT_GEOM_RECT_XY ? 1 : 2;
+    const double xi1 = path_draw(seed, cell, i, 4u + 2u * light);
+    const double xi2 = path_draw(seed, cell, i, 5u + 2u * light);
+    y[d1] = q.p[0] + xi1 * (q.p[1] - q.p[0]);
+    y[d2] = q.p[2] + xi2 * (q.p[3] - q.p[2]);
+    y[3 - d1 - d2] = q.p[4];
+  }
+  for (int a = 0; a < 3; ++a) w[a] = y[a] - x[a];
+  return (w[0] * w[0] + w[1] * w[1]) + w[2] * w[2] > 0.0;
 }
 
 int compile_scene(const rt_scene_desc* d, int32_t builder, const SceneTuning& tune, CompiledScene* out,

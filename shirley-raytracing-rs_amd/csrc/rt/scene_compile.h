@@ -106,7 +106,21 @@ struct LightGridTable {
 };
 // RT_OK, or RT_E_INVALID for cells outside 1 ... 64 or a table of more than 2^22 entries.  No light: RT_OK, all
 // of `info` zero, no row.
-int build_light_grid(const LightList& l, int32_t cells, bool want_cdf, LightGridTable* out);
+// `masks` (may be null; [cells][L] words of `rays` bits, rt_scene_light_visibility): the rows then follow the
+// visibility-weighted rule of the header; without them the call is rt_scene_light_pick's, bit for bit.
+int build_light_grid(const LightList& l, int32_t cells, bool want_cdf, LightGridTable* out,
+                     const uint32_t* masks = nullptr, int32_t rays = 0);
+
+// The path's draw `draw` of (seed, pixel, sample) on the host: the device's rng_next on Rng{pixel, sample, draw}.
+double path_draw(uint64_t seed, uint32_t pixel, uint32_t sample, uint32_t draw);
+// Ray i of (cell, light) in the grid `g` (rt_scene_light_visibility; include/shirley_rt.h): x[3] the cell point,
+// w[3] the vector to the light's target (0 from inside a sphere light); true when the ray is traced, false when
+// the bit is set without one.
+bool light_visibility_ray(const rt_light_grid& g, const DLight& q, uint64_t seed, uint32_t cell, uint32_t light,
+                          uint32_t i, double* x, double* w);
+inline bool light_visibility_rays_ok(int32_t rays) {
+  return rays == 1 || rays == 2 || rays == 4 || rays == 8 || rays == 16 || rays == 32;
+}
 
 // What rt_scene_upload copies to the device and records in the context.
 struct CompiledScene {

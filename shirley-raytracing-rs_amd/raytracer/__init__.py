@@ -11,5 +11,5 @@ from .scene import (SceneBuilder, Scene, TextureLoader, Metal, Dielectric, Lambe
 from .camera import CameraBuilder, CameraPosition, default_camera, cornell_camera, scene_camera  # noqa: F401
 from .render import (Device, RenderSettings, AdaptiveSettings, Comm, render_scene, render_multi, comm_unique_id, scene_digest, to_image,  # noqa: F401
                      to_image_counts, write_png, tile_layout, DenoiseSettings, denoise, moments_variance, light_grid_host,
-                     light_sample_host)
+                     light_sample_host, light_visibility_rays_host, light_visibility_rows_host)
 from . import scenes  # noqa: F401

@@ -142,6 +142,12 @@ class rt_light_sample(C.Structure):  # a light sample before its shadow ray (add
                 ("cx", C.c_double), ("cy", C.c_double), ("g_plain", C.c_double), ("g_mis", C.c_double)]
 
 
+class rt_light_visibility(C.Structure):  # the report of rt_scene_light_visibility (added within ABI 11)
+    _fields_ = [("rays", C.c_int32), ("pad", C.c_int32), ("seed", C.c_uint64), ("pairs", C.c_uint64),
+                ("traced", C.c_uint64), ("unoccluded", C.c_uint64), ("dead_points", C.c_uint64),
+                ("kernel_ms", C.c_double)]
+
+
 class rt_bvh_node(C.Structure):
     _fields_ = [("box", _d6), ("leaf", C.c_int32), ("lhs", C.c_int32), ("rhs", C.c_int32), ("pad", C.c_int32)]
 
@@ -255,6 +261,13 @@ RT_SIGNATURES = {
                                      C.POINTER(rt_light_sample)]),
     "rt_light_sample_host": (C.c_int, [C.POINTER(rt_scene_desc), C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
                                        C.c_void_p, C.c_uint64, C.POINTER(rt_light_sample)]),
+    # added within ABI 11: the visibility-aware light pick
+    "rt_scene_light_visibility": (C.c_int, [C.c_void_p, C.c_int32, C.c_uint64, C.POINTER(rt_light_visibility)]),
+    "rt_light_visibility_masks": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "rt_light_visibility_rays_host": (C.c_int, [C.POINTER(rt_scene_desc), C.c_int32, C.c_int32, C.c_uint64, C.c_int32,
+                                                C.c_int32, C.c_void_p, C.c_void_p]),
+    "rt_light_visibility_rows_host": (C.c_int, [C.POINTER(rt_scene_desc), C.c_int32, C.c_int32, C.c_void_p,
+                                                C.c_void_p]),
 }
 
 # every symbol declared in include/shirley_host.h

@@ -399,6 +399,23 @@ class Device:
                                                      prob.ctypes.data))
         return light[:len(p)], prob[:len(p)]
 
+    def light_visibility(self, rays: int, seed: int) -> N.rt_light_visibility:
+        """rt_scene_light_visibility: traces `rays` (1, 2, 4, 8, 16 or 32) shadow rays from every cell of the grid
+        last set by light_pick to every listed light and weights the rows by what they saw, until the next
+        upload(), light_pick() or light_visibility(); rays = 0 puts the plain rows back.  Returns the report."""
+        rep = N.rt_light_visibility()
+        _check(self._h, N.rt_lib().rt_scene_light_visibility(self._h, int(rays), int(seed), C.byref(rep)))
+        self._light_vis_pairs = int(rep.pairs)  # (the size of light_visibility_masks' buffer)
+        return rep
+
+    def light_visibility_masks(self) -> np.ndarray:
+        """rt_light_visibility_masks: the masks the device traced for the setting in force, flat [cells][n_lights]
+        uint32 in the grid of the last light_pick (bit i: ray i of the pair)."""
+        pairs = getattr(self, "_light_vis_pairs", 0)
+        masks = np.zeros(max(1, pairs), dtype=np.uint32)
+        _check(self._h, N.rt_lib().rt_light_visibility_masks(self._h, masks.ctypes.data))
+        return masks[:pairs]
+
     def light_sampling(self, mode: int) -> None:
         """rt_scene_light_sampling: how render_direct / render_nee sample a light until the next upload():
         N.RT_LIGHT_SAMPLE_AREA (a point of its area), N.RT_LIGHT_SAMPLE_SOLID_ANGLE (a sphere light: a direction of
@@ -505,6 +522,33 @@ def light_grid_host(scene: Scene, cells: int):
         if code:
             raise N.RtError(code, "rt_light_grid_host failed")
     return info, cdf
+
+
+def light_visibility_rays_host(scene: Scene, cells: int, rays: int, seed: int, cell: int, light: int):
+    """rt_light_visibility_rays_host -> (rays [K][6] f64 = x, w; traced [K] uint8): the K rays of one (cell, light)
+    pair of Device.light_visibility(rays, seed) after light_pick(cells), in plain C++ (no device needed)."""
+    out = np.zeros((max(1, int(rays)), 6), dtype=np.float64)
+    traced = np.zeros(max(1, int(rays)), dtype=np.uint8)
+    code = N.rt_lib().rt_light_visibility_rays_host(scene.desc_ptr, int(cells), int(rays), int(seed), int(cell),
+                                                    int(light), out.ctypes.data, traced.ctypes.data)
+    if code:
+        raise N.RtError(code, "rt_light_visibility_rays_host: invalid scene, cells, rays, cell or light")
+    return out[:int(rays)], traced[:int(rays)]
+
+
+def light_visibility_rows_host(scene: Scene, cells: int, rays: int, masks):
+    """rt_light_visibility_rows_host -> cdf [n[2]][n[1]][n[0]][n_lights] f64: the rows Device.light_visibility
+    builds from these masks ([cells][n_lights] uint32), in plain C++ (no device needed)."""
+    info, _ = light_grid_host(scene, cells)
+    m = np.ascontiguousarray(masks, dtype=np.uint32).reshape(-1)
+    cdf = np.zeros((info.n[2], info.n[1], info.n[0], info.n_lights), dtype=np.float64)
+    if m.size != cdf.size or not cdf.size:
+        raise ValueError("one mask per (cell, light) of a scene that lists a light")
+    code = N.rt_lib().rt_light_visibility_rows_host(scene.desc_ptr, int(cells), int(rays), m.ctypes.data,
+                                                    cdf.ctypes.data)
+    if code:
+        raise N.RtError(code, "rt_light_visibility_rows_host: invalid scene, cells or rays")
+    return cdf
 
 
 def _vertices(points, normals):
