@@ -161,6 +161,102 @@ def test_hit_queries_match_golden(gpu):
             assert abs(g.u - gold["record"][i][7]) < 1e-12 and abs(g.v - gold["record"][i][8]) < 1e-12
 
 
+@pytest.mark.parametrize("nt", ["4", "6"])
+def test_split_engine_traversal_wave_counts(gpu, monkeypatch, nt):
+    """RT_ENGINE_SPLIT's other two instances (split_supported_nt: 4 and 6 traversal waves of the block's 16; 8 is the
+    default) with a refill threshold of 3 idle lanes (SHIRLEY_SPLIT_NT, SHIRLEY_SPLIT_REFILL, read at upload): the
+    megakernel's frame, bit for bit."""
+    spp = 4
+    s = dict(samples=spp, max_reflect=50, seed=SEED, sample_chunk=spp)
+    for name, width, aspect in [("random", 48, "std16x9"), ("perlin", 48, "std16x9")]:
+        scene = rt.SceneBuilder.builtin(name, SEED).finalize(SEED)
+        cam = rt.scene_camera(name, width, aspect)
+        monkeypatch.setenv("SHIRLEY_SPLIT_NT", nt)
+        monkeypatch.setenv("SHIRLEY_SPLIT_REFILL", "3")
+        gpu.upload(scene)
+        monkeypatch.delenv("SHIRLEY_SPLIT_NT")
+        monkeypatch.delenv("SHIRLEY_SPLIT_REFILL")
+        img = gpu.render(cam, rt.RenderSettings(**s, engine="split"))
+        c = gpu.counters()
+        assert c.engine == 3
+        mk = gpu.render(cam, rt.RenderSettings(**s, engine="megakernel"))
+        cm = gpu.counters()
+        assert cm.engine == 1 and np.array_equal(img, mk), name
+        assert (c.samples, c.segments) == (cm.samples, cm.segments)
+        gpu.upload(scene)  # (the refill threshold stays with the context until an upload sets it: back to 8 waves)
+
+
+@pytest.mark.parametrize("window", ["64", "1024"])
+def test_wavefront_extend_window(gpu, window, monkeypatch):
+    """wf_extend4's cursor claims in windows of 64 and of 1024 slots (SHIRLEY_WF_WINDOW, read at the call; 256 by
+    default) on a 4096-slot pool: the megakernel's frame and path counters, as test_wavefront_small_slot_pool."""
+    monkeypatch.setenv("SHIRLEY_WF_SLOTS", "4096")
+    spp = 6
+    for name, width, aspect in [("perlin", 40, "std16x9"), ("cornell", 24, "square")]:
+        scene = rt.SceneBuilder.builtin(name, SEED).finalize(SEED)
+        cam = rt.scene_camera(name, width, aspect)
+        gpu.upload(scene)
+        a = gpu.render(cam, rt.RenderSettings(samples=spp, seed=SEED, sample_chunk=2, engine="megakernel"))
+        ca = gpu.counters()
+        monkeypatch.setenv("SHIRLEY_WF_WINDOW", window)
+        b = gpu.render(cam, rt.RenderSettings(samples=spp, seed=SEED, sample_chunk=2, engine="wavefront"))
+        monkeypatch.delenv("SHIRLEY_WF_WINDOW")
+        cb = gpu.counters()
+        assert cb.engine == 2 and np.array_equal(a, b), name
+        assert 64 <= cb.slots <= 4096 and cb.iterations > 1
+        assert (ca.samples, ca.segments) == (cb.samples, cb.segments)
+
+
+@pytest.mark.parametrize("name,switch,width,aspect", [("random", "SHIRLEY_SAH_BINNED", 48, "std16x9"),
+                                                      ("cornell", "SHIRLEY_SAH_BOXW", 40, "square")])
+def test_sah_builder_switches_match_oracle(gpu, monkeypatch, name, switch, width, aspect):
+    """The binned SAH sweep and the unweighted RectBox cost (SHIRLEY_SAH_BINNED, SHIRLEY_SAH_BOXW=1, read at upload)
+    build another tree than the default SAH one, so the reference is the oracle: the frame by the parity rule with
+    the scene's floor, and 2048 rays through both traversals, record for record."""
+    from test_gpu_traversal import _check_against_oracle, random_scene_rays, scene_box_rays
+    import json
+    import os
+    with open(os.path.join(os.path.dirname(__file__), "golden", "scene_plan.json")) as f:
+        plans = json.load(f)["cases"]
+    spp = 8
+    scene = rt.SceneBuilder.builtin(name, SEED).finalize(SEED)
+    cam = rt.scene_camera(name, width, aspect)
+    from raytracer import _native as N
+
+    def sah_tree():
+        """The SAH tree as the library builds it now (rt_bvh_build_host: tuning_from_env and build_tree, as the
+        upload), as bytes."""
+        n = C.c_int32(0)
+        assert N.rt_lib().rt_bvh_build_host(scene.desc_ptr, N.RT_BVH_SAH, C.byref(n), None, None) == 0
+        arr, root = (N.rt_bvh_node * n.value)(), C.c_int32(0)
+        assert N.rt_lib().rt_bvh_build_host(scene.desc_ptr, N.RT_BVH_SAH, C.byref(n), arr, C.byref(root)) == 0
+        return bytes(arr), root.value
+
+    s = rt.RenderSettings(samples=spp, max_reflect=50, seed=SEED, sample_chunk=spp, engine="megakernel")
+    default_tree = sah_tree()
+    monkeypatch.setenv(switch, "1")
+    gpu.upload(scene, "sah")
+    switch_tree = sah_tree()
+    monkeypatch.delenv(switch)
+    # the switch was read: the library builds another tree under it, the fixture (tests/test_scene_plan.py) holds
+    # another 4-wide tree under it than the default SAH one, and the uploaded tree has that one's sizes
+    assert switch_tree != default_tree
+    dflt, var = plans[f"{name}/0x5EED/sah/default"], plans[f"{name}/0x5EED/sah/default/{switch[8:]}=1"]
+    st = gpu.stats()
+    assert var["fnv"]["nodes4"] != dflt["fnv"]["nodes4"]
+    sizes = ("n_nodes", "n_nodes4", "n_leaves", "depth")
+    assert tuple(getattr(st, k) for k in sizes) == tuple(var[k] for k in sizes)
+    osc = O.OracleScene(scene)
+    ora, ocnt = osc.render(cam, O.params(spp, 50, SEED))
+    img = gpu.render(cam, s)
+    check_parity(img, ora, spp, frac_exact=exact_floor(name))
+    assert gpu.counters().samples == ocnt.samples
+    rays = random_scene_rays(2048) if name == "random" else scene_box_rays(scene, cam, 2048)
+    for traversal in ("render", "binary"):
+        _check_against_oracle(gpu.hit(rays, 0.001, float("inf"), traversal=traversal), rays, osc, 500)
+    gpu.upload(scene)
+
+
 @pytest.mark.parametrize("slots", ["64", "4096"])
 def test_wavefront_small_slot_pool(gpu, slots, monkeypatch):
     """Far fewer path slots than work units: every slot regenerates many paths and takes many
@@ -412,7 +508,7 @@ def test_edge_cases(gpu, engine):
 
 
 @pytest.mark.parametrize("engine", ENGINES)
-def test_full_size_rows_match_oracle(gpu, engine):
+def test_full_size_rows_match_oracle(gpu, engine, monkeypatch):
     """BASELINE config 2 geometry (1200x800, random_scene) at reduced spp: two full rows against the
     oracle, plus the size-independent property full-frame row == rt_render_scanlines row."""
     spp = 6
@@ -422,11 +518,20 @@ def test_full_size_rows_match_oracle(gpu, engine):
     gpu.upload(scene)
     s = rt.RenderSettings(engine=engine, samples=spp, seed=SEED, sample_chunk=spp)
     full = gpu.render(cam, s)
+    assert gpu.counters().samples == 1200 * 800 * spp
     rows = gpu.render_scanlines(cam, s, 200, 202)
     assert np.array_equal(rows, full[200:202])
     ora, _ = O.OracleScene(scene).render(cam, O.params(spp, 50, SEED), 200, 202)
     check_parity(rows, ora, spp)
     assert np.isfinite(full).all() and (full >= 0).all()
+    # no unit lost or served twice anywhere in the frame: the sample count, and the whole frame against the shared
+    # queue's (SHIRLEY_SEGMENTS=0, read at the call; six-sample units get per-block segments of several windows by
+    # default), which the rows above tie to the oracle
+    monkeypatch.setenv("SHIRLEY_SEGMENTS", "0")
+    queue = gpu.render(cam, s)
+    monkeypatch.delenv("SHIRLEY_SEGMENTS")
+    assert gpu.counters().samples == 1200 * 800 * spp
+    assert np.array_equal(queue[200:202], rows) and np.array_equal(queue, full)
 
 
 def test_device_tonemap_matches_host(gpu):

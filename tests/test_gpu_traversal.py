@@ -31,6 +31,29 @@ def _same_record(g, h):
             and bool(g.front_face) == bool(h.front_face))
 
 
+def random_scene_rays(n, seed=1):
+    """n rays among random_scene's spheres: origins in the slab above the ground, normal directions."""
+    rng = np.random.default_rng(seed)
+    orig = np.column_stack([rng.uniform(-12, 12, n), rng.uniform(0.05, 3, n), rng.uniform(-12, 12, n)])
+    return np.hstack([orig, rng.normal(size=(n, 3))])
+
+
+def scene_box_rays(scene, cam, n, seed=5):
+    """n rays at a scene of any size: half from around the camera towards points of the scene box, half from
+    inside the box (a huge ground sphere: the region around the origin)."""
+    eye = np.array(cam.origin)
+    nodes, root = O.OracleScene(scene).tree()
+    box = np.array(nodes[root][0])
+    lo, hi = box[:3], box[3:]
+    if (hi - lo).max() > 5000:  # a huge ground sphere: aim at the region around the origin
+        lo, hi = np.maximum(lo, -50.0), np.minimum(hi, 50.0)
+    rng = np.random.default_rng(seed)
+    target = lo + (hi - lo) * rng.uniform(size=(n, 3))
+    orig = np.where((np.arange(n) % 2 == 0)[:, None], eye + rng.normal(scale=1.0, size=(n, 3)),
+                    lo + (hi - lo) * rng.uniform(size=(n, 3)))
+    return np.hstack([orig, target - orig])
+
+
 def _check_against_oracle(hits, rays, osc, min_hits):
     n_hit = 0
     for i in range(len(rays)):
@@ -68,10 +91,7 @@ def test_render_traversal_matches_oracle(gpu, nodes, bvh):
     scene = rt.scenes.random_scene(SEED).finalize(SEED)
     gpu.upload(scene, bvh, nodes)
     osc = O.OracleScene(scene)
-    rng = np.random.default_rng(1)
-    n = 4096
-    orig = np.column_stack([rng.uniform(-12, 12, n), rng.uniform(0.05, 3, n), rng.uniform(-12, 12, n)])
-    rays = np.hstack([orig, rng.normal(size=(n, 3))])
+    rays = random_scene_rays(4096)
     hits = gpu.hit(rays, 0.001, float("inf"), traversal="render")
     _check_against_oracle(hits, rays, osc, 1000)
     # and identical to the 2-wide f64 traversal, record for record
@@ -136,20 +156,7 @@ def test_render_traversal_rect_box_and_book2_scenes(gpu, name, nodes):
     for record, and == the oracle for reference primitives."""
     scene = rt.SceneBuilder.builtin(name, SEED).finalize(SEED)
     gpu.upload(scene, nodes=nodes)
-    cam = rt.scene_camera(name, 32, "square")
-    eye = np.array(cam.origin)
-    nodes, root = O.OracleScene(scene).tree()
-    box = np.array(nodes[root][0])
-    lo, hi = box[:3], box[3:]
-    if (hi - lo).max() > 5000:  # a huge ground sphere: aim at the region around the origin
-        lo, hi = np.maximum(lo, -50.0), np.minimum(hi, 50.0)
-    rng = np.random.default_rng(5)
-    n = 2048
-    target = lo + (hi - lo) * rng.uniform(size=(n, 3))
-    # half the rays from around the camera towards points of the scene box, half from inside the box
-    orig = np.where((np.arange(n) % 2 == 0)[:, None], eye + rng.normal(scale=1.0, size=(n, 3)),
-                    lo + (hi - lo) * rng.uniform(size=(n, 3)))
-    rays = np.hstack([orig, target - orig])
+    rays = scene_box_rays(scene, rt.scene_camera(name, 32, "square"), 2048)
     a = gpu.hit(rays, 0.001, float("inf"), traversal="render")
     b = gpu.hit(rays, 0.001, float("inf"), traversal="binary")
     n_hit = 0
