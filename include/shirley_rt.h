@@ -721,6 +721,61 @@ int rt_render_nee(rt_ctx* ctx, const rt_camera* cam, const rt_render_params* par
 int rt_render_nee_device(rt_ctx* ctx, const rt_camera* cam, const rt_render_params* params, int32_t flags,
                          double* accum_dev, void* stream);
 
+/* ---- the adaptive light-sampling render --------------------------------------------
+ * Added within ABI 11 like the light list: purely additive, RT_ABI_VERSION stays 11.
+ *
+ * rt_render_nee_adaptive is rt_render_adaptive's contract with rt_render_nee's samples, rendered by one kernel
+ * launch: the wave that owns an 8x8 tile keeps the tile's statistics and takes the stop decision itself.
+ * `flags` means what it means for rt_render_nee; the scene's light pick, light sampling mode and light
+ * visibility settings apply as they do there.  params / adaptive are checked as for rt_render_adaptive: the batch
+ * b = params->sample_chunk (0 means 4); params->samples (the per-pixel maximum), min_samples and step are
+ * multiples of b; min_samples >= 2 b; sample_begin and sample_count are 0 and tile_world is 1.  engine and
+ * scratch_mb are ignored.
+ *
+ *   samples     Sample s of pixel p is rt_render_nee's sample (seed, p, s).  The batch sum B_k(p) is the in-order
+ *               sum of samples [k b, (k + 1) b) of p from (0, 0, 0): what rt_render_nee returns for that sample
+ *               range, bit for bit.
+ *   sums        A pixel that received n batches holds accum_c = ((0 + B_0.c) + B_1.c) + ... + B_(n-1).c per
+ *               channel c, and, with y_k = (B_k.r + B_k.g) + B_k.b, the moments
+ *               m1 = ((0 + y_0) + y_1) + ... + y_(n-1);  m2 = fma(y_k, y_k, m2) for k = 0 ... n-1 from m2 = 0
+ *               (one rounding per batch) — rt_render_adaptive's sums, with rt_render_nee's batch sums.
+ *   checks      A tile is checked when all its in-image pixels hold N = min_samples samples, then after every
+ *               further `step`, the last one clipped at params->samples.  At a check after n = N / b batches:
+ *                 v_p = max(0, m2_p - m1_p * m1_p / (double)n) / (double)(n - 1)  per in-image pixel p;
+ *                 E = sum v_p, M = sum m1_p, K = the number of in-image pixels, each summed over the tile's 64
+ *                 lanes (lane l = pixel (l % 8, l / 8) of the tile, out-of-image lanes contributing 0) by six
+ *                 rounds off = 32, 16, 8, 4, 2, 1 in which every lane l adds lane (l ^ off)'s value to its own;
+ *                 e = 0 if E == 0, else sqrt((double)n * E / K) / (M / K + ((double)n * b) * noise_floor).
+ *               The tile goes on iff (!(e <= threshold) || threshold == 0) and N < params->samples.
+ *   outputs     counts = N at the tile's last check, for every in-image pixel of the tile; tile_error = e at that
+ *               check.  Threshold 0 stops no tile; +inf stops every tile with a finite e at min_samples; a NaN
+ *               e renders to params->samples.
+ * max_depth <= 0 gives zero sums, zero moments, counts = min_samples and e = 0; no segment is traced.
+ * Every in-image element of every output is written by the call.  The result does not depend on which wave
+ * renders which tile or on the size of the grid.
+ *
+ * rt_render_nee_adaptive blocks.  report (may be NULL): steps = 1 + ceil((largest count - min_samples) / step);
+ * tiles = the tiles of the frame; tiles_converged = the tiles with e <= threshold at their last check (at
+ * threshold 0 that counts the tiles with e == 0, all-sky tiles for one, although threshold 0 stopped none of them);
+ * samples = the sum of counts; kernel_ms = the launch's event time; segments = 0 (this pass does not count
+ * segments) and fold_ms = 0 (there is no fold).  rt_render_nee_adaptive_device takes device pointers (accum,
+ * counts and moments required) and is asynchronous on `stream` (NULL: the context's stream) with no host
+ * synchronisation; the tile counter is one word of the context, so at most one such call per context may be in
+ * flight: issue the next on the same stream, or after the earlier one has completed.  rt_moments_variance,
+ * rt_tonemap_counts and rt_denoise take the outputs as they take rt_render_adaptive's.  RT_E_INVALID: a failed check of params / adaptive, unknown flag bits, a NULL required
+ * buffer.  Scenes with book-2 objects return RT_E_UNSUPPORTED.  Not available through the multi-GPU entry points;
+ * not checkpointed. */
+int rt_render_nee_adaptive(rt_ctx* ctx, const rt_camera* cam, const rt_render_params* params, int32_t flags,
+                           const rt_adaptive_params* adaptive,
+                           double* accum_host,      /* [H][W][3] sums over each pixel's own samples, row 0 = bottom */
+                           int32_t* counts_host,    /* [H][W] samples the pixel received */
+                           double* moments_host,    /* [H][W][2] m1, m2; may be NULL */
+                           double* tile_error_host, /* [tiles] as rt_render_adaptive's; may be NULL */
+                           rt_adaptive_report* report /* may be NULL */);
+int rt_render_nee_adaptive_device(rt_ctx* ctx, const rt_camera* cam, const rt_render_params* params, int32_t flags,
+                                  const rt_adaptive_params* adaptive, double* accum_dev, int32_t* counts_dev,
+                                  double* moments_dev, double* tile_error_dev /* may be NULL */, void* stream);
+
 /* ---- the spatially weighted light pick ---------------------------------------------
  * Added within ABI 11 like the light list: purely additive, RT_ABI_VERSION stays 11.
  *

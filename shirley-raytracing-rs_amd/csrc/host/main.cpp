@@ -28,6 +28,9 @@
 // --nee [--nee-mis 0|1]: the light-sampling path integrator (rt_render_nee; --nee-mis 1, the default, weights
 // light sample and scatter by the balance heuristic) in place of the colour render, with the usual -s / -m;
 // the same restrictions as --direct, and not together with it.
+// --nee-adaptive T (with --nee): the adaptive light-sampling render (rt_render_nee_adaptive) — --adaptive's rule
+// with --min-samples, --adaptive-step, --noise-floor and --sample-chunk, applied inside the one launch; the
+// picture divides every pixel by its own sample count; --nee's restrictions.
 // --light-grid N (with --nee or --direct): the spatially weighted light pick (rt_scene_light_pick) with N cells,
 // 1 ... 64, along the light grid's longest axis; 0, the default, is the uniform pick.
 // --light-visibility K (with --light-grid N >= 1): K shadow rays per cell and light weight the grid's rows
@@ -69,6 +72,8 @@ struct Args {
   int direct_chain = 8;
   bool nee = false;  // --nee: the light-sampling path integrator in place of the colour render
   int nee_mis = 1;
+  bool nee_adaptive = false;  // --nee-adaptive T: rt_render_nee_adaptive in place of rt_render_nee
+  double nee_adaptive_threshold = 0.0;
   int light_grid = 0;  // --light-grid N: the light pick of --nee / --direct (0: uniform)
   bool light_grid_given = false;
   int light_visibility = 0;  // --light-visibility K: shadow rays per (cell, light) of the grid (0: off)
@@ -95,6 +100,7 @@ struct Args {
                "         --ao RADIUS|inf --ao-chain K\n"
                "         --direct --direct-chain K\n"
                "         --nee --nee-mis 0|1\n"
+               "         --nee-adaptive T (with --nee; --min-samples N --adaptive-step N --noise-floor F --sample-chunk N)\n"
                "         --light-grid N (with --nee or --direct; 0 ... 64 cells, 0 = uniform pick)\n"
                "         --light-visibility K (with --light-grid N >= 1: 1, 2, 4, 8, 16 or 32 shadow rays per cell and light)\n"
                "         --light-cone (with --nee or --direct: sphere lights sampled by solid angle)\n"
@@ -422,6 +428,32 @@ int render_scene(const Args& a, const rt_scene_desc* desc, const rt_camera& cam)
   } else if (a.nee) {
     // the light-sampling path integrator in place of the colour render: the same sums, through the tonemap
     accum.resize(n);
+    if (a.nee_adaptive) {  // tiles stop at their own sample count, the picture divides by the counts
+      rt_adaptive_params ap{};
+      ap.min_samples = a.min_samples;
+      ap.step = a.adaptive_step;
+      ap.threshold = a.nee_adaptive_threshold;
+      ap.noise_floor = a.noise_floor;
+      std::vector<int32_t> counts(n / 3);
+      rt_adaptive_report rep{};
+      if ((st = rt_render_nee_adaptive(ctx, &cam, &p, a.nee_mis ? RT_NEE_MIS : 0, &ap, accum.data(), counts.data(),
+                                       nullptr, nullptr, &rep))) {
+        std::fprintf(stderr, "error: --nee-adaptive: %s\n", rt_last_error(ctx));
+        rt_destroy(ctx);
+        return 1;
+      }
+      rt_tonemap_counts(accum.data(), counts.data(), cam.image_width, cam.image_height, rgb.data());
+      rt_destroy(ctx);
+      if (verbose >= 1)
+        std::fprintf(stderr, "INFO adaptive: %d steps, mean %.2f spp of at most %d, %.1f %% of %d tiles converged\n",
+                     rep.steps, (double)rep.samples / (double)(n / 3), samples,
+                     100.0 * rep.tiles_converged / (double)(rep.tiles ? rep.tiles : 1), rep.tiles);
+      if (sh_write_png(a.output.c_str(), rgb.data(), cam.image_width, cam.image_height)) {
+        std::fprintf(stderr, "error: %s\n", sh_last_error());
+        return 1;
+      }
+      return 0;
+    }
     if ((st = rt_render_nee(ctx, &cam, &p, a.nee_mis ? RT_NEE_MIS : 0, accum.data()))) {
       std::fprintf(stderr, "error: --nee: %s\n", rt_last_error(ctx));
       rt_destroy(ctx);
@@ -633,6 +665,7 @@ int main(int argc, char** argv) {
     else if (s == "--direct") a.direct = true;
     else if (s == "--direct-chain") a.direct_chain = std::atoi(next().c_str());
     else if (s == "--nee") a.nee = true;
+    else if (s == "--nee-adaptive") { a.nee_adaptive = true; a.nee_adaptive_threshold = std::atof(next().c_str()); }
     else if (s == "--nee-mis") {
       const std::string v = next();
       a.nee_mis = v == "0" ? 0 : v == "1" ? 1 : -1;
@@ -671,6 +704,11 @@ int main(int argc, char** argv) {
   if (a.progressive < 1) usage("--progressive must be >= 1");
   if (a.gpus > 1 && (a.progressive > 1 || !a.resume.empty())) usage("--progressive / --resume render on one GPU");
 
+  if (a.nee_adaptive && !a.nee) usage("--nee-adaptive sets the stop rule of --nee");
+  if (a.nee_adaptive && (a.gpus > 1 || a.progressive > 1 || !a.resume.empty() || !a.dump_accum.empty()))
+    usage("--nee-adaptive renders on one GPU, without --progressive / --resume / --dump-accum");
+  if (a.nee_adaptive && (a.adaptive || a.denoise >= 0 || a.ao > 0.0 || a.direct))
+    usage("--nee-adaptive is --nee's own stop rule: no --adaptive, no --denoise, no --ao, no --direct");
   if (a.nee && (a.gpus > 1 || a.progressive > 1 || !a.resume.empty()))
     usage("--nee renders on one GPU, without --progressive / --resume");
   if (a.nee && (a.adaptive || a.denoise >= 0 || a.ao > 0.0 || a.direct))

@@ -505,7 +505,7 @@ int rt_destroy(rt_ctx* c) {
   if (!c) return RT_OK;
   (void)hipSetDevice(c->device);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
-  for (DevBuf* b : {&c->nodes, &c->nodes4, &c->prims, &c->mats, &c->texs, &c->perlin, &c->texels, &c->exts, &c->ground, &c->planes, &c->lights, &c->prim_light, &c->light_cdf, &c->light_vis_out, &c->partial, &c->kcam, &c->shutter0, &c->moments, &c->tile_list, &c->tile_err, &c->dn_a, &c->dn_b, &c->feat,
+  for (DevBuf* b : {&c->nodes, &c->nodes4, &c->prims, &c->mats, &c->texs, &c->perlin, &c->texels, &c->exts, &c->ground, &c->planes, &c->lights, &c->prim_light, &c->light_cdf, &c->light_vis_out, &c->partial, &c->kcam, &c->shutter0, &c->moments, &c->tile_list, &c->tile_err, &c->nee_adapt, &c->nee_moments, &c->dn_a, &c->dn_b, &c->feat,
                     &c->accum, &c->counters, &c->unit_counter, &c->wf_pool, &c->wf_iters, &c->packed, &c->gathered,
                     &c->parts, &c->band, &c->digests})
     release(*b);

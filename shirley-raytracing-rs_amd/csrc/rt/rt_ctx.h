@@ -83,6 +83,9 @@ struct rt_ctx {
   // per-render scratch
   DevBuf partial, accum, counters, unit_counter, kcam;
   DevBuf moments, tile_list, tile_err;  // rt_render_adaptive: [H][W][2] moments, a step's tile list and its errors
+  // rt_render_nee_adaptive: the tile counter's word, then (host form) the [H][W] counts; the moments of a host
+  // call that asked for none
+  DevBuf nee_adapt, nee_moments;
   DevBuf dn_a, dn_b;  // rt_denoise_device: the two [H][W][12] record buffers an iteration reads / writes
   DevBuf feat;        // rt_render_features: the device buffers behind the host copies
   DevBuf shutter0;  // {0, 0}: the shutter of rt_scene_hit / rt_probe_segment queries (DScene.shutter)

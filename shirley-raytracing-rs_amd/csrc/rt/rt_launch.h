@@ -1,7 +1,7 @@
 // rt_launch.h — the launch wrappers of the HIP files, as the host side of the C ABI calls them.
 //
 // Included by rt_api.cpp, rt_multi.cpp, rt_denoise.cpp and by the files that define the wrappers (trace.hip,
-// trace_split.hip, wavefront.hip, features.hip, denoise.hip, occlusion.hip, direct.hip, nee.hip), so a changed
+// trace_split.hip, wavefront.hip, features.hip, denoise.hip, occlusion.hip, direct.hip, nee.hip, nee_adaptive.hip), so a changed
 // signature fails to compile where it is changed.  The wrappers of the tile passes and of the ray batches
 // (launch_features, _occluded, _ao, _direct, _nee, _hit4, _probe) keep their own argument checks and place and
 // launch their kernel through pass_frame.h (dispatch_placement, block_lds_bytes, launch_block).
@@ -66,6 +66,19 @@ hipError_t launch_light_sample(const DLight* lights, int n_lights, const DLightG
 hipError_t launch_nee(const DScene& S, bool wide, bool mis, const DCamera& C, uint64_t seed, int s_begin, int s_end,
                       int max_depth, const DLight* lights, int n_lights, const DLightGrid* grid, int sample,
                       const int32_t* prim_light, double* accum, hipStream_t stream);
+// nee_adaptive.hip: the adaptive arguments of nee_kernel's ADAPT instances (rt_render_nee_adaptive)
+struct NeeAdapt {
+  unsigned* counter;  // the next tile to hand out: cleared on the stream before the launch
+  double* moments;    // [H][W][2] m1, m2
+  double* tile_err;   // [tiles] e at the tile's last check, or null
+  int32_t* counts;    // [H][W]
+  int batch, min_samples, step;
+  double threshold, noise_floor;
+};
+hipError_t launch_nee_adaptive(const DScene& S, bool wide, bool mis, const DCamera& C, uint64_t seed, int samples,
+                               int max_depth, const DLight* lights, int n_lights, const DLightGrid* grid, int sample,
+                               const int32_t* prim_light, double* accum, const NeeAdapt& ad, int cu_count,
+                               int max_blocks, hipStream_t stream);
 // trace_split.hip
 bool split_supported_nt(int nt);
 hipError_t split_prepare(const DScene& S, int nt, int* blocks_per_cu);

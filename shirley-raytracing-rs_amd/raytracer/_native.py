@@ -251,6 +251,13 @@ RT_SIGNATURES = {
                                 C.c_void_p]),
     "rt_render_nee_device": (C.c_int, [C.c_void_p, C.POINTER(rt_camera), C.POINTER(rt_render_params), C.c_int32,
                                        C.c_void_p, C.c_void_p]),
+    # added within ABI 11: the adaptive light-sampling render
+    "rt_render_nee_adaptive": (C.c_int, [C.c_void_p, C.POINTER(rt_camera), C.POINTER(rt_render_params), C.c_int32,
+                                         C.POINTER(rt_adaptive_params), C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.POINTER(rt_adaptive_report)]),
+    "rt_render_nee_adaptive_device": (C.c_int, [C.c_void_p, C.POINTER(rt_camera), C.POINTER(rt_render_params),
+                                                C.c_int32, C.POINTER(rt_adaptive_params), C.c_void_p, C.c_void_p,
+                                                C.c_void_p, C.c_void_p, C.c_void_p]),
     # added within ABI 11: the spatially weighted light pick
     "rt_light_grid_host": (C.c_int, [C.POINTER(rt_scene_desc), C.c_int32, C.POINTER(rt_light_grid), C.c_void_p]),
     "rt_scene_light_pick": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(rt_light_grid)]),

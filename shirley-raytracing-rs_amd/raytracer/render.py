@@ -378,6 +378,34 @@ class Device:
                                                         N.RT_NEE_MIS if mis else 0, C.c_void_p(accum_ptr or None),
                                                         C.c_void_p(stream or None)))
 
+    def render_nee_adaptive(self, camera: N.rt_camera, settings: RenderSettings, adaptive: AdaptiveSettings,
+                            mis: bool = True):
+        """rt_render_nee_adaptive -> render_adaptive's tuple (accum, counts, moments, tile_error, report): one
+        launch of the light-sampling integrator in which the wave that owns an 8x8 tile applies render_adaptive's
+        stop rule; a pixel with n samples holds render_nee's samples [0, n), added batch by batch."""
+        h, w = camera.image_height, camera.image_width
+        accum = np.zeros((h, w, 3), dtype=np.float64)
+        counts = np.zeros((h, w), dtype=np.int32)
+        moments = np.zeros((h, w, 2), dtype=np.float64)
+        tile_error = np.zeros(((h + 7) // 8, (w + 7) // 8), dtype=np.float64)
+        report = N.rt_adaptive_report()
+        p, a = settings.params(), adaptive.params()
+        _check(self._h, N.rt_lib().rt_render_nee_adaptive(
+            self._h, C.byref(camera), C.byref(p), N.RT_NEE_MIS if mis else 0, C.byref(a), accum.ctypes.data,
+            counts.ctypes.data, moments.ctypes.data, tile_error.ctypes.data, C.byref(report)))
+        return accum, counts, moments, tile_error, report
+
+    def render_nee_adaptive_device(self, camera, settings: RenderSettings, adaptive: AdaptiveSettings, mis: bool,
+                                   accum_ptr: int, counts_ptr: int, moments_ptr: int, tile_error_ptr: int = 0,
+                                   stream: int = 0):
+        """rt_render_nee_adaptive_device: device [H][W][3] f64, [H][W] int32, [H][W][2] f64 and (or 0) [tiles] f64
+        outputs; asynchronous on `stream`."""
+        p, a = settings.params(), adaptive.params()
+        _check(self._h, N.rt_lib().rt_render_nee_adaptive_device(
+            self._h, C.byref(camera), C.byref(p), N.RT_NEE_MIS if mis else 0, C.byref(a),
+            C.c_void_p(accum_ptr or None), C.c_void_p(counts_ptr or None), C.c_void_p(moments_ptr or None),
+            C.c_void_p(tile_error_ptr or None), C.c_void_p(stream or None)))
+
     def light_pick(self, cells: int) -> N.rt_light_grid:
         """rt_scene_light_pick: how render_direct / render_nee pick their one light per vertex until the next
         upload().  cells = 0: uniformly; 1 ... 64: from the light grid with that many cells along its longest

@@ -4,6 +4,12 @@
 #   object:  default the in-tree build's trace.hip.o
 #   pattern: awk regex on the mangled kernel name, default trace_kernel (the megakernel instances);
 #            e.g. tools/kstats.sh shirley-raytracing-rs_amd/build/rt/direct.hip.o direct_kernel
+# After a compiler update, re-check that the uniform nee_kernel instances (ADAPT = false, nee.hip.o) are what they
+# were (their tile loop is a backward jump for the sake of these figures):
+#   tools/kstats.sh shirley-raytracing-rs_amd/build/rt/nee.hip.o nee_kernel | sed 's/^[^ ]* *//' \
+#     | diff - <(sed 's/^[^ ]* *//' profiles/nee_adaptive/kstats_new.txt)
+# (an empty diff: all 60 keep their VGPRs, spills, SGPRs and scratch; if a new compiler moves them anyway, compare
+# against a build of the kernel without the ADAPT parts before blaming the jump).
 # Each line ends with the static LDS (`lds N`), which listings made before this field existed do not have.
 obj=${1:-shirley-raytracing-rs_amd/build/rt/trace.hip.o}
 pat=${2:-trace_kernel}
